@@ -607,6 +607,34 @@ def respawn_one_rank_per_gpu(n):
     os.execv(sys.executable, cmd)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240
+
+
+def device_outputs(net):
+    """What a forward leaves for its caller in the net's device buffers (value, policy probabilities, auxiliary outputs), on the host."""
+    torch.cuda.synchronize()
+    return {name: torch.as_tensor(view, device="cuda").cpu().numpy()
+            for name, view in net.device_buffers().items() if name in ("value", "probs", "aux")}
+
+
+def write_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """arrays (name -> [batch, ...]) as <out_dir>/<name>.npy in float32.  Above `limit` bytes in all, every array keeps the same seeded
+    sample of boards, whose indices go to boards.npy (float64), so that two runs with the same arguments write the same boards."""
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float32) for name, a in arrays.items()}
+    batch = next(iter(arrays.values())).shape[0]
+    per_board = sum(a.nbytes for a in arrays.values()) // batch
+    if per_board * batch > limit:
+        keep = limit // (per_board + 8)
+        boards = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(batch, size=keep, replace=False))
+        arrays = {name: a[boards] for name, a in arrays.items()}
+        arrays["boards"] = boards.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return arrays
+
+
 def timed_mode_leg(local_rank, batch, model_dir, precision, x, steps, flops_peak):
     """One more precision mode on the same workload (N = 1 information, never `value`): evals/s, ms per step, achieved TFLOP/s."""
     from crazyara_amd.neuralnetapi import HipAPI
@@ -646,8 +674,10 @@ def main():
                          "reference's TensorRT default (its logits miss 1e-3 by 2-3x); float32: exact-f32 MFMA")
     ap.add_argument("--blocks", type=int, default=N_BLOCKS)
     ap.add_argument("--batch", type=int, default=BATCH)
-    ap.add_argument("--min-timed-seconds", type=float, default=0.5,
-                    help="the timed region of --steps steps is repeated until the repeats add up to this; ms_per_step = the median repeat")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last step computed (value, policy probabilities, auxiliary outputs: what "
+                         "a caller of the path receives) as DIR/<name>.npy in float32, at most 64 MB in all; with the same arguments the "
+                         "inputs are the same from run to run, so that two builds can be compared output for output")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-search", action="store_true")
     ap.add_argument("--simulations", type=int, default=1600)
@@ -793,15 +823,16 @@ def main():
 
     for _ in range(0 if dry else args.warmup):
         net.forward_device()
-    # A 20-step request is 7 ms of GPU time: one region decides nothing.  The region is repeated (same K steps each, barrier-bracketed
-    # each) until the repeats add up to --min-timed-seconds; `ms_per_step` / `value` are the MEDIAN repeat, all repeats are reported.
-    evals, first = timed_region()
-    n_rep = max(1, min(400, int(np.ceil(args.min_timed_seconds / max(first, 1e-6)))))    # from the reduced time: every rank agrees
-    regions = [first] + [timed_region()[1] for _ in range(n_rep - 1)]
+    # one region of exactly --steps steps: a short request is a noisy one, and the caller chooses its length
+    evals, elapsed = timed_region()
+    regions = [elapsed]
     if dist is not None:
         dist.barrier()
-    elapsed = float(np.median(regions))
     value = evals / elapsed
+    if args.dump_outputs and rank == 0:
+        written = write_outputs(args.dump_outputs, device_outputs(net))
+        print(f"bench: the last timed step's outputs written to {args.dump_outputs}: "
+              + ", ".join(f"{k} {list(a.shape)}" for k, a in written.items()), file=sys.stderr)
 
     # ---- MCTS leg (BASELINE config 2: batch 256, 1600 simulations per search, fixed opening set) ----
     # Timed region >= 1 s: rounds of "every tree restarts from its next opening position and is searched to 1600 simulations" until

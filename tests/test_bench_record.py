@@ -5,6 +5,8 @@ import json
 import os
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -102,3 +104,65 @@ def test_line_limit_holds_for_an_oversized_result_and_for_legs_without_rates():
     assert len(json.dumps(line)) < bench.LINE_LIMIT
     assert line["roofline"]["frac"] == full["roofline"]["frac"] and line["cpu_baseline"]["value"] == full["cpu_baseline"]["value"]
     assert line["summary"]["nn_evals_per_sec"] == full["value"]
+
+
+def test_written_outputs_are_float32_and_a_seeded_sample_above_the_limit(tmp_path):
+    """--dump-outputs: every array of the last timed step goes out as float32; above the limit every array keeps the same boards, the
+    same ones on every call (two builds compared output for output must look at the same boards)."""
+    import numpy as np
+
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = {"value": rng.standard_normal(64).astype(np.float32), "probs": rng.random((64, 100), dtype=np.float32),
+              "aux": rng.standard_normal((64, 4)).astype(np.float64)}
+    written = bench.write_outputs(str(tmp_path / "all"), arrays)
+    assert sorted(written) == ["aux", "probs", "value"]
+    for name, a in arrays.items():
+        back = np.load(tmp_path / "all" / f"{name}.npy")
+        assert back.dtype == np.float32 and np.array_equal(back, a.astype(np.float32))
+    limit = 20 * (1 + 100 + 4) * 4 + 20 * 8                                   # room for 20 of the 64 boards
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), arrays, limit=limit)
+    boards = np.load(tmp_path / "a" / "boards.npy")
+    assert boards.dtype == np.float64 and len(boards) == 20 and np.array_equal(boards, np.load(tmp_path / "b" / "boards.npy"))
+    assert np.all(np.diff(boards) > 0) and 0 <= boards[0] and boards[-1] < 64
+    rows = boards.astype(np.int64)
+    total = 0
+    for name, a in arrays.items():
+        back = np.load(tmp_path / "a" / f"{name}.npy")
+        assert back.dtype == np.float32 and np.array_equal(back, a[rows].astype(np.float32))
+        assert np.array_equal(back, np.load(tmp_path / "b" / f"{name}.npy"))
+        total += back.nbytes
+    assert total + boards.nbytes <= limit
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_what_the_timed_steps_computed(tmp_path, hip_lib):
+    """bench.py --dump-outputs on a small net: the timed region is exactly --steps steps, the dumped value and policy are the oracle's on
+    the bench's seeded inputs, and a second run with the same arguments writes the same bits."""
+    import subprocess
+
+    import numpy as np
+
+    import bench
+    from crazyara_amd import rise_config
+    from oracle import rise_oracle as ro
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--timed-only",
+                            "--blocks", "3", "--batch", "16", "--precision", "float32", "--detail-out", str(tmp_path / f"detail_{run}.json"),
+                            "--dump-outputs", str(tmp_path / run)], cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    for line in lines:
+        assert line["steps"] == 7 and line["timed_region"]["repeats"] == 1
+    assert sorted(os.listdir(tmp_path / "a")) == ["probs.npy", "value.npy"]
+    for name in ("value", "probs"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy"))
+    cfg = rise_config.rise_v2_config(3, 34, 81)
+    sd = rise_config.make_state_dict(cfg, seed=2024, stress=True)
+    v, p, _ = ro.predict(cfg, sd, bench.synthetic_planes(16, cfg.nb_input_channels, seed=7))
+    value, probs = np.load(tmp_path / "a" / "value.npy"), np.load(tmp_path / "a" / "probs.npy")
+    assert value.dtype == probs.dtype == np.float32 and value.shape == (16,) and probs.shape == (16, cfg.nb_policy)
+    assert np.abs(value - v.numpy().reshape(-1)).max() < 1e-4 and np.abs(probs - p.numpy()).max() < 1e-4

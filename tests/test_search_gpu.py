@@ -1,5 +1,7 @@
 """GPU: the whole hot path end to end -- position -> 192-byte descriptor -> GPU plane builder -> RISE forward -> policy
 gather in the leaf collector -- against the oracle chain (oracle planes -> oracle NN -> oracle policy index)."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -272,13 +274,15 @@ def test_nets_of_one_process_work_on_different_hardware_queues(tmp_path, hip_lib
     """Round 6: nets take their stream from a per-device set the library keeps (one per hardware queue, never destroyed), the one unused
     the longest -- not a stream created per net, whose hardware queue depended on how many idle nets the process still held
     (scripts/ubench/stream_queues.hip).  Four nets open at once work in four different streams; a fifth shares the one that has been
-    idle the longest; a net that is closed frees nothing that matters; every net still computes the same numbers in whichever stream."""
+    idle the longest; a net that is closed frees nothing that matters; every net still computes the same numbers in whichever stream.
+    The number of hardware queues is the runtime's (GPU_MAX_HW_QUEUES, 4 when unset), read once per process: the set the library made
+    for an earlier test of this session has as many streams as the environment gives queues, so the test counts with that number."""
     from crazyara_amd import _capi
     cfg, sd, _ = nn_cases.make_case("risev2-7")
     d = nn_cases.export_case(tmp_path, "risev2-7", cfg, sd)
     lib = _capi.load()
     monkeypatch.delenv("CRA_OWN_STREAM_PER_NET", raising=False)
-    monkeypatch.delenv("GPU_MAX_HW_QUEUES", raising=False)
+    n_queues = min(16, max(1, int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))))     # as take_net_stream() in rise_net.hip
     x = np.ascontiguousarray(torch.rand(8, cfg.nb_input_channels, 8, 8).numpy())
 
     def run(n):
@@ -287,24 +291,24 @@ def test_nets_of_one_process_work_on_different_hardware_queues(tmp_path, hip_lib
         n.predict(x, v, p, np.full(8 * 4, 7.0, np.float32) if cfg.nb_aux else None)
         return v, p
 
-    nets = [HipAPI(0, 8, d, "float16") for _ in range(4)]
+    nets = [HipAPI(0, 8, d, "float16") for _ in range(n_queues)]
     streams = [lib.mi_net_stream(n._h) for n in nets]
-    assert len(set(streams)) == 4
+    assert len(set(streams)) == n_queues
     ref = run(nets[0])
     for n in nets[1:]:
         out = run(n)
         assert all(np.array_equal(a, b) for a, b in zip(ref, out))
-    # nets[0] predicted first of the four: its stream is the one unused the longest now
-    fifth = HipAPI(0, 8, d, "float16")
-    assert lib.mi_net_stream(fifth._h) == streams[0]
-    assert all(np.array_equal(a, b) for a, b in zip(ref, run(fifth)))
-    nets[1].close()
-    sixth = HipAPI(0, 8, d, "float16x3")          # a float16x3 net made for 8 boards (several launches, a captured graph)
-    assert lib.mi_net_stream(sixth._h) in streams
+    # nets[0] predicted first of them: its stream is the one unused the longest now
+    extra = HipAPI(0, 8, d, "float16")
+    assert lib.mi_net_stream(extra._h) == streams[0]
+    assert all(np.array_equal(a, b) for a, b in zip(ref, run(extra)))
+    nets[-1].close()
+    x3 = HipAPI(0, 8, d, "float16x3")             # a float16x3 net made for 8 boards (several launches, a captured graph)
+    assert lib.mi_net_stream(x3._h) in streams
     o_value, o_logits, _ = ro.forward(cfg, sd, torch.from_numpy(x))
-    v6 = run(sixth)[0]
-    assert np.abs(v6 - o_value.numpy().reshape(-1)).max() < 1e-4
-    for n in (nets[0], nets[2], nets[3], fifth, sixth):
+    vx = run(x3)[0]
+    assert np.abs(vx - o_value.numpy().reshape(-1)).max() < 1e-4
+    for n in nets[:-1] + [extra, x3]:
         n.close()
     monkeypatch.setenv("CRA_OWN_STREAM_PER_NET", "1")
     own = HipAPI(0, 8, d, "float16")
