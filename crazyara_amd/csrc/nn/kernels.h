@@ -46,7 +46,7 @@ struct ConvArgs {
     const float* planes;
     int planes_c;
     // Precision float16p8 (x3.hip: conv3x3_p8_kernel; ks = 3, cin a multiple of 128): wpk = f16 image of w * 2^p, wpk_lo = the 8-bit image of the
-    // cross terms (rise_net.hip: pack_dense_p8), acc_scale = 2^-p
+    // cross terms (pack.cpp: pack_dense_p8), acc_scale = 2^-p
     int p8;
     float acc_scale;
     // float16p8, the policy head of a policy-map net in one launch (conv3x3_p8_chain_kernel): the conv 3x3 256 -> 256 + BN + ReLU in FRONT of this
@@ -95,16 +95,16 @@ int block_x3_chunk_channels();
 // by the caller's SE launch)
 struct X3TowerBlock {
     const void *w1pk, *w1pk_lo, *w3pk, *w3pk_lo;     // as BlockArgs
-    const float* dwpk;                               // [cop_pad / 16 tiles][16 rows: taps dx = -1 (dy = -1, 0, 1), dx = 0, dx = +1, BN1 bias, BN2 bias, 5 x 0][16 channels] (rise_net.hip: pack_x3_depthwise_records)
+    const float* dwpk;                               // [cop_pad / 16 tiles][16 rows: taps dx = -1 (dy = -1, 0, 1), dx = 0, dx = +1, BN1 bias, BN2 bias, 5 x 0][16 channels] (pack.cpp: pack_x3_depthwise_records)
     const float* b3;                                 // [256]
-    const float* se_w1t;                             // gate matrices in THREAD order (x3.hip: x3_se_phase; rise_net.hip: pack_se_threads_f32):
+    const float* se_w1t;                             // gate matrices in THREAD order (x3.hip: x3_se_phase; pack.cpp: pack_se_threads_f32):
     const float* se_w2t;                             //   ca_se: W1 then W2, 16 float4 loads per thread each; eca_se: se_w1t = both halves
     const float* se_b;                               // eca_se: [256]
     int cop_pad;                                     // multiple of block_x3_chunk_channels()
     int se_kind;                                     // 0 none, 1 ca_se, 2 eca_se
     // Precision float16p8 (x3.hip, tower_p8_kernel): w1pk / w3pk = f16 image of w * 2^p (p per layer), w1pk_lo / w3pk_lo = the 8-bit image of the cross
     // terms (per cout tile and 64 k: lanes' 32 bytes [e5m2((w * 2^p) - hi) for 64 k ; e5m2(hi) for the same 64 k], both times the truncation
-    // compensation, bytes 0-15 in "slab" 2 J, bytes 16-31 in "slab" 2 J + 1 of the lo image's geometry; rise_net.hip: pack_dense_p8).  w1_inv = 2^-p1
+    // compensation, bytes 0-15 in "slab" 2 J, bytes 16-31 in "slab" 2 J + 1 of the lo image's geometry; pack.cpp: pack_dense_p8).  w1_inv = 2^-p1
     // brings the expand accumulators back in front of the BN1 bias; the residual stream runs in the project weights' scale inside a block:
     // x := (x + b3) * w3_scale, + the project sums, x := x * w3_inv (powers of two: exact)
     float w1_inv, w3_scale, w3_inv;
@@ -151,7 +151,7 @@ template <typename T> int block_chunk_channels();   // C_op must be padded to a 
 
 // Residual tower: a run of consecutive 3x3 bottleneck blocks in one launch, one workgroup per board, residual stream
 // resident in LDS, SE gates computed in-kernel (tower.hip).  f16 only, C = 256, C_op padded to whole chunks of 128.
-// The conv weights of the whole run are packed into per-wave streams in consumption order (rise_net.hip):
+// The conv weights of the whole run are packed into per-wave streams in consumption order (pack.cpp):
 //   wstream  4 matrix waves x fragments of 64 lanes x 8 halves = v_mfma_f32_32x32x16_f16 A operands (lane l, element j:
 //            row l%32, k (l/32)*8 + j).  Per block, per interval k = -1..n: 16 expand fragments of chunk k+1 ([k-step of 16],
 //            rows = channels chunk*128 + w*32 + row), then 16 project fragments of chunk k-1 ([k-step of 16][row tile of 32],
@@ -166,7 +166,7 @@ constexpr int kTowerWindow = 16;
 struct TowerBlockDesc {
     const float* b3;      // [256] BN3 bias (Precision fp8: divided by s3)
     const float* s3;      // Precision fp8: [256] power-of-two scale of the project weights per cout (y = x + s3 * acc); else nullptr
-    const void* se_w1;    // f16 pairs in thread order (rise_net.hip: pack_se_threads; tower.hip: se_phase): ca_se W1, or the eca_se centre-tap
+    const void* se_w1;    // f16 pairs in thread order (pack.cpp: pack_se_threads; tower.hip: se_phase): ca_se W1, or the eca_se centre-tap
                           // matrix in two halves; or nullptr
     const void* se_w2;    // f16 pairs in thread order: ca_se W2
     const float* se_b;    // eca_se bias [256]

@@ -272,7 +272,7 @@ struct Linear {
     std::string out;
 };
 
-constexpr float kLoaderBnVar = 0.99999f;   // running_var such that var + kBnEps (rise_net.hip) == 1
+constexpr float kLoaderBnVar = 0.99999f;   // running_var such that var + kBnEps (pack.h) == 1
 
 class Importer {
 public:

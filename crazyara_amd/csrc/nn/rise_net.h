@@ -27,6 +27,26 @@ struct RiseDesign {
 uint8_t float_to_e4m3(float v);
 uint8_t float_to_e5m2(float v);
 
+// What a precision string selects (parse_precision, rise_net.hip): the arithmetic and the kernel-family variants.  Every suffix combines
+// with every mode when parsed; "-unfused" also drops the tower.  Which combinations a model can run is decided when the net is built
+// (fp8 / int8 need the one-launch bottleneck tower, the suffixes that name a kernel family only act where that family runs).
+struct Precision {
+    enum class Mode { Float32, Float16, Float16x3, Float16p8, Fp8, Int8 };
+    Mode mode = Mode::Float16;
+    bool fused = true;         // "-unfused": the layer-granular kernels (A/B reference for the fused block kernel); also no tower
+    bool tower = true;         // "-perblock": one launch per bottleneck block (A/B reference for the tower kernel)
+    bool one_launch = true;    // stem + tower + head in one launch when the net is exactly that chain ("-3k": three launches)
+    bool thin_waves = false;   // dense residual tower: 8 waves x 32 couts ("-8w") instead of 4 x 64
+    bool board_split = true;   // float16x3 / float16p8 small batches run split-board blocks ("-1wg": one workgroup per board)
+    int boards_per_wg = 0;     // dense residual tower: 0 = by batch size (2 from 512 boards), 1 / 2 = forced ("-1b" / "-2b")
+    bool fp16() const { return mode == Mode::Float16 || mode == Mode::Fp8 || mode == Mode::Int8; }   // f16 activations (else float)
+    bool x3() const { return mode == Mode::Float16x3 || mode == Mode::Float16p8; }    // split-operand f16 MFMAs (x3.hip)
+    bool p8() const { return mode == Mode::Float16p8; }       // float16x3 whose tower takes the 1x1 GEMMs' cross terms through e5m2 MFMAs
+    bool fp8_tower() const { return mode == Mode::Fp8 || mode == Mode::Int8; }       // 8-bit operands in the tower's GEMMs
+    bool int8() const { return mode == Mode::Int8; }           // the calibrated INT8 mode (tower.hip Q = 2)
+};
+Precision parse_precision(const std::string& precision);   // throws std::invalid_argument
+
 class RiseNet {
 public:
     // model_path: a .cranet file, or a directory searched like get_onnx_model_name() (neuralnetapi.cpp:57-73).
@@ -46,7 +66,7 @@ public:
     const RiseDesign& design() const { return design_; }
     const std::string& model_name() const { return model_name_; }
     const std::string& model_file_path() const { return model_file_path_; }
-    bool fp16() const { return fp16_; }
+    bool fp16() const { return prec_.fp16(); }
     int device() const { return device_; }
     hipStream_t stream() const { return stream_; }
 
@@ -116,6 +136,7 @@ public:
 
 private:
     struct Impl;
+    template <typename T> struct Builder;   // the stages of build() over one state (rise_net.hip)
     template <typename T> void build(const NetFile& nf);
     template <typename T> void enqueue(hipStream_t s, const IoOverride* io = nullptr);
     template <typename T> void launch_op(int i, hipStream_t s, const IoOverride* io = nullptr);
@@ -137,11 +158,17 @@ private:
         bool lane_sync = false;         // CRA_LANE_SYNC: a stream sync between forward and gather
         bool x3_symmetric = false;      // CRA_X3_TOWER=symmetric: the float16x3 tower with every wave running all three phases
         int x3_split_dev = 0;           // CRA_X3_SPLIT_DEV: timing switches of block_x3_split_kernel (x3.hip; bits 2 and 4 give wrong results)
-        int x3_split_max_g = 0;         // CRA_X3_SPLIT_MAX_G: upper bound on the workgroups per board of the split-board blocks
-        int x3_split_max_batch = 0;     // CRA_X3_SPLIT_MAX_BATCH: the largest batch that runs split-board (default kBoardSplitMaxBatch)
         bool no_small_path = false;     // CRA_NO_SMALL_PATH: partial batches run the whole batch's forward as before round 6 (A/B)
         int small_conv_split = 2;       // CRA_SMALL_BATCH_CONV_SPLIT: the wide convs of a small-batch net as 1 = two workgroups of 128 couts per board, 2 = four of 64
         bool own_stream = false;        // CRA_OWN_STREAM_PER_NET: a stream created (and destroyed) per net, as before the streams of the library (A/B)
+        // what build() reads
+        bool tower_trace = false;       // CRA_TOWER_TRACE: the tower / head kernels record s_memtime stamps (kernels.h: TowerArgs::trace)
+        bool x3_value_one_launch;       // CRA_X3_VALUE_HEAD=one / three: the float16x3 value head as value_head_kernel or three launches
+        bool value_head_debug = false;  // CRA_VALUE_HEAD_DEBUG: value_head_kernel's stage checksums (value_head_debug())
+        int value_head_lds_pad = -1;    // CRA_VALUE_HEAD_LDS_PAD: kernels.h: ValueHeadArgs::lds_pad
+        int value_head_variant = 0;     // CRA_VALUE_HEAD_VARIANT: kernels.h: ValueHeadArgs::variant
+        bool x3_no_head_chain = false;  // CRA_X3_NO_HEAD_CHAIN: the float16x3 policy head as two launches
+        bool small_batch_heads_apart = false;   // CRA_SMALL_BATCH_HEADS_APART: a small batch's policy conv and value head as two launches
         DevSwitches();
     } dev_;
     float* value_head_dbg_ = nullptr;
@@ -150,19 +177,12 @@ private:
 
     RiseDesign design_;
     std::string model_name_, model_file_path_;
-    bool fp16_ = true;
-    bool x3_ = false;            // Precision float16x3: float activations, split-operand f16 MFMAs (x3.hip); fp16_ is false
-    bool p8_ = false;            // Precision float16p8: float16x3 whose one-launch tower takes the cross terms of both 1x1 GEMMs through e5m2 MFMAs
-    bool fp8_tower_ = false;     // Precision fp8 / int8: 8-bit operands in the residual tower's GEMMs, everything else as float16
-    bool int8_ = false;          // Precision int8: the calibrated INT8 mode (tower.hip Q = 2); fp8_tower_ is set too (same streams and tiles)
+    Precision prec_;
     std::vector<std::pair<float, float>> int8_calib_;   // per block: max |stream in front of it|, max depthwise output (read_int8_calibration)
-    bool fused_ = true;
-    bool tower_ = true;
     // Small batches (round 6): float16x3 / float16p8 nets made for at most kBoardSplitMaxBatch boards (64: measured faster up to 96, profiles/r06/d_*) run their 3x3 bottleneck blocks one per
     // launch with up to C_op / 128 workgroups per board (x3.hip: block_x3_split_kernel, float16x3 arithmetic in both modes) instead of the
     // one-workgroup-per-board tower, whose latency a small batch pays in full on a handful of CUs.  "-1wg" after the precision keeps the
     // one-workgroup-per-board tower (A/B, and the parity tests of the tower kernels on the small fixtures).
-    bool board_split_ = true;
     static constexpr int kBoardSplitMaxBatch = 64;
     // A net made for MORE boards still meets small batches: the root of a `go` (one board), the first batches of a single tree, the tail of
     // a game loop.  submit_boards / submit_boards_gathered with at most kBoardSplitMaxBatch valid boards go to a companion net of that batch
@@ -176,9 +196,6 @@ private:
     int dyn_n_ = 0, dyn_prev_g_ = 1;  // > 0 while a forward of dyn_n_ boards is being enqueued (launch_op)
     bool small_path_ok() const;
     RiseNet& small_net();
-    bool one_launch_ = true;     // stem + tower + head in one launch when the net is exactly that chain ("-3k": three launches)
-    bool rt_thin_waves_ = false; // dense residual tower: 8 waves x 32 couts ("-8w") instead of 4 x 64
-    int boards_per_wg_ = 0;      // dense residual tower: 0 = by batch size (2 from 512 boards), 1 / 2 = forced ("-1b" / "-2b")
     struct Turn;                       // forwards of different streams take turns when one fills the chip (rise_net.hip)
     int cu_count_ = 256;
     int device_ = 0;
