@@ -58,6 +58,8 @@ struct ConvArgs {
                           // tile request no weight fragments
     int few_boards;       // the net was made for a small batch (board-split forward): the couts of a wide layer go over several workgroups per
                           // board -- 1: two of 128 couts, 2: four of 64 (RiseNet::DevSwitches::small_conv_split)
+    int x_ld;             // row pitch of `x` in elements, 0 = cin (conv_gemm_kernel, conv_gemm_x3_kernel): a conv that reads the first cin
+                          // channels of a wider tile (the transformer block's projection reads the E_MHSA part of its C-wide output)
 };
 
 template <typename T> void launch_conv_gemm(const ConvArgs& a, hipStream_t s);
@@ -372,6 +374,18 @@ template <typename T> void launch_value_final(const ValueFinalArgs& a, hipStream
 // the batch's values (and aux) out.
 void launch_gather_probs(const float* probs, int nb_policy, const uint16_t* idx, const uint32_t* cnt, int stride, int n_slots, float* out,
                          const float* value_dev, float* value_out, int batch, const float* aux_dev, float* aux_out, hipStream_t s);
+
+// Attention core of a NextViT transformer block (attention.hip): per board and head of 32 channels, softmax(Q K^T * 32^-0.5) V over the
+// 64 squares.  qkv: [B][64][3D] T (q = channels 0 .. D-1, k = D .. 2D-1, v = 2D .. 3D-1; head h = channels 32 h .. 32 h + 31 of each),
+// out: [B][64][D] T.  mode 0: float16 (T = half_t), 1: float32 (T = float, exact f32 MFMA), 2: float16x3 (T = float, hi / lo split operands).
+struct AttentionArgs {
+    const void* qkv;
+    void* out;
+    int batch;
+    int D;                // multiple of 32
+    int mode;
+};
+void launch_attention(const AttentionArgs& a, hipStream_t s);
 
 // row softmax over n logits per board (tensorrtapi.cpp:378-392 appends exactly this to policy_out)
 void launch_softmax(const float* logits, float* probs, int batch, int n, hipStream_t s);

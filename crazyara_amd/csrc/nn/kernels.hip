@@ -37,7 +37,8 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvArgs a) {
     const int l15 = lane & 15, lg = lane >> 4;
     const int co_tile = blockIdx.x * 4 + wave;
     const bool active = co_tile * 16 < a.cout_pad;
-    const T* xb = reinterpret_cast<const T*>(a.x) + size_t(b) * kSquares * a.cin;
+    const int x_ld = a.x_ld ? a.x_ld : a.cin;
+    const T* xb = reinterpret_cast<const T*>(a.x) + size_t(b) * kSquares * x_ld;
     const int nslab_ci = a.cin >> 5;
     const int nslab = KS * KS * nslab_ci;
     const frag* wp = reinterpret_cast<const frag*>(a.wpk) + size_t(active ? co_tile : 0) * nslab * 64 + lane;
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvArgs a) {
         const int vec_per_row = kcl * int(sizeof(T)) / 16;
         for (int i = tid; i < kSquares * vec_per_row; i += 256) {
             const int r = i / vec_per_row, v = i - r * vec_per_row;
-            const uint4 d = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(xb + size_t(r) * a.cin + kc0) + v * 16);
+            const uint4 d = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(xb + size_t(r) * x_ld + kc0) + v * 16);
             *reinterpret_cast<uint4*>(reinterpret_cast<char*>(xs + r * ROWP) + v * 16) = d;
         }
         __syncthreads();

@@ -33,6 +33,111 @@ BlockFold fold_block(const NetFile& nf, const std::string& p) {
     return BlockFold{fold_bn(nf, p + ".body.0", p + ".body.1"), fold_bn(nf, p + ".body.3", p + ".body.4"), fold_bn(nf, p + ".body.6", p + ".body.7")};
 }
 
+namespace {
+void expect_shape(const NetFile& nf, const std::string& name, std::vector<int64_t> shape) {
+    if (!nf.has(name)) throw std::runtime_error("transformer block: tensor " + name + " is missing");
+    if (nf.get(name).shape != shape) {
+        std::string want;
+        for (int64_t d : shape) want += (want.empty() ? "" : "x") + std::to_string(d);
+        throw std::runtime_error("transformer block: tensor " + name + " has the wrong shape (expected " + want + ")");
+    }
+}
+void expect_bn(const NetFile& nf, const std::string& bn, int64_t c) {
+    for (const char* t : {".weight", ".bias", ".running_mean", ".running_var"}) expect_shape(nf, bn + t, {c});
+}
+// a Linear / 1x1 conv with bias, no BN behind it
+Folded load_biased(const NetFile& nf, const std::string& name) {
+    Folded f = fold_bn(nf, name, "");
+    const TensorView& b = nf.get(name + ".bias");
+    for (int64_t i = 0; i < b.numel(); ++i) f.b[i] = b.data[i];
+    return f;
+}
+// merge_pre_bn: y = W BN(x) + b = (W diag(s)) x + (b + W (beta - s mean)), s = gamma / sqrt(var + eps); W is [cout][cin]
+void fold_pre_bn(Folded& f, const NetFile& nf, const std::string& bn, int cin) {
+    const float *g = nf.get(bn + ".weight").data, *be = nf.get(bn + ".bias").data, *m = nf.get(bn + ".running_mean").data,
+                *v = nf.get(bn + ".running_var").data;
+    const int cout = int(f.b.size());
+    for (int co = 0; co < cout; ++co) {
+        double extra = 0.0;
+        for (int ci = 0; ci < cin; ++ci) {
+            const double sc = double(g[ci]) / std::sqrt(double(v[ci]) + kBnEps);
+            extra += f.w[size_t(co) * cin + ci] * (double(be[ci]) - double(m[ci]) * sc);
+            f.w[size_t(co) * cin + ci] *= sc;
+        }
+        f.b[co] += extra;
+    }
+}
+}  // namespace
+
+NtbFold fold_ntb(const NetFile& nf, const std::string& p, int C) {
+    NtbFold n;
+    n.C = C;
+    if (!nf.has(p + ".projection.conv.weight") && !nf.has(p + ".mhca.group_conv3x3.weight") && nf.has(p + ".e_mhsa.q.weight"))
+        throw std::runtime_error("transformer block " + p + ": the 'simple' NTB variant (no projection / MHCA branch) is not supported");
+    if (nf.has(p + ".e_mhsa.norm.weight") || nf.has(p + ".e_mhsa.norm.running_mean"))
+        throw std::runtime_error("transformer block " + p + ": E_MHSA with sr_ratio > 1 (e_mhsa.norm present) is not supported");
+    if (!nf.has(p + ".patch_embed.conv.weight")) throw std::runtime_error("transformer block: tensor " + p + ".patch_embed.conv.weight is missing");
+    const TensorView& pe = nf.get(p + ".patch_embed.conv.weight");
+    if (pe.shape.size() != 4 || pe.shape[1] != C || pe.shape[2] != 1 || pe.shape[3] != 1)
+        throw std::runtime_error("transformer block: tensor " + p + ".patch_embed.conv.weight has the wrong shape (expected Dx" + std::to_string(C) + "x1x1)");
+    n.D = int(pe.shape[0]);
+    n.M = C - n.D;
+    if (n.D % 32 != 0 || n.M <= 0 || n.M % 32 != 0)
+        throw std::runtime_error("transformer block " + p + ": E_MHSA width " + std::to_string(n.D) + " of " + std::to_string(C) +
+                                 " channels is not a head_dim-32 split (both parts must be multiples of 32)");
+    const int D = n.D, M = n.M;
+    expect_bn(nf, p + ".patch_embed.norm", D);
+    expect_bn(nf, p + ".norm1", D);
+    for (const char* l : {".e_mhsa.q", ".e_mhsa.k", ".e_mhsa.v", ".e_mhsa.proj"}) {
+        expect_shape(nf, p + l + ".weight", {D, D});
+        expect_shape(nf, p + l + ".bias", {D});
+    }
+    expect_shape(nf, p + ".projection.conv.weight", {M, D, 1, 1});
+    expect_bn(nf, p + ".projection.norm", M);
+    if (!nf.has(p + ".mhca.group_conv3x3.weight")) throw std::runtime_error("transformer block: tensor " + p + ".mhca.group_conv3x3.weight is missing");
+    const TensorView& gc = nf.get(p + ".mhca.group_conv3x3.weight");
+    if (gc.shape.size() != 4 || gc.shape[0] != M || gc.shape[2] != 3 || gc.shape[3] != 3)
+        throw std::runtime_error("transformer block: tensor " + p + ".mhca.group_conv3x3.weight has the wrong shape (expected " + std::to_string(M) + "x32x3x3)");
+    if (gc.shape[1] != 32)
+        throw std::runtime_error("transformer block " + p + ": head_dim " + std::to_string(gc.shape[1]) + " (MHCA group width) is not supported, only 32");
+    expect_bn(nf, p + ".mhca.norm", M);
+    expect_shape(nf, p + ".mhca.projection.weight", {M, M, 1, 1});
+    expect_bn(nf, p + ".norm2", C);
+    if (!nf.has(p + ".mlp.conv1.weight")) throw std::runtime_error("transformer block: tensor " + p + ".mlp.conv1.weight is missing");
+    n.H = int(nf.get(p + ".mlp.conv1.weight").shape[0]);
+    expect_shape(nf, p + ".mlp.conv1.weight", {n.H, C, 1, 1});
+    expect_shape(nf, p + ".mlp.conv1.bias", {n.H});
+    expect_shape(nf, p + ".mlp.conv2.weight", {C, n.H, 1, 1});
+    expect_shape(nf, p + ".mlp.conv2.bias", {C});
+    if (n.H % 32 != 0) throw std::runtime_error("transformer block " + p + ": Mlp hidden width must be a multiple of 32");
+
+    n.patch = fold_bn(nf, p + ".patch_embed.conv", p + ".patch_embed.norm");
+    n.qkv.w.reserve(size_t(3) * D * D);
+    for (const char* l : {".e_mhsa.q", ".e_mhsa.k", ".e_mhsa.v"}) {
+        Folded f = load_biased(nf, p + l);
+        fold_pre_bn(f, nf, p + ".norm1", D);
+        n.qkv.w.insert(n.qkv.w.end(), f.w.begin(), f.w.end());
+        n.qkv.b.insert(n.qkv.b.end(), f.b.begin(), f.b.end());
+    }
+    n.proj = load_biased(nf, p + ".e_mhsa.proj");
+    n.projection = fold_bn(nf, p + ".projection.conv", p + ".projection.norm");
+    {   // grouped 3x3 (groups = M / 32) as a dense 3x3 that is zero off the diagonal blocks
+        const Folded g = fold_bn(nf, p + ".mhca.group_conv3x3", p + ".mhca.norm");
+        n.mhca.w.assign(size_t(M) * M * 9, 0.0);
+        n.mhca.b = g.b;
+        for (int co = 0; co < M; ++co)
+            for (int j = 0; j < 32; ++j)
+                for (int t = 0; t < 9; ++t) n.mhca.w[(size_t(co) * M + (co / 32) * 32 + j) * 9 + t] = g.w[(size_t(co) * 32 + j) * 9 + t];
+    }
+    n.mhca_proj = fold_bn(nf, p + ".mhca.projection", "");
+    n.mlp1 = load_biased(nf, p + ".mlp.conv1");
+    fold_pre_bn(n.mlp1, nf, p + ".norm2", C);
+    n.mlp2 = load_biased(nf, p + ".mlp.conv2");
+    const double sq = 64.0;
+    n.macs = sq * C * D + sq * D * 3.0 * D + 2.0 * sq * 64.0 * D + sq * D * D + sq * D * M + sq * M * 32.0 * 9 + sq * M * M + 2.0 * sq * C * n.H;
+    return n;
+}
+
 // float -> OCP e4m3fn byte: round to nearest even, subnormals down to 2^-9, beyond +-448 clamps (the device conversion runs with
 // MODE.FP16_OVFL = 1 and does the same)
 uint8_t to_e4m3(double v) {

@@ -26,6 +26,25 @@ Folded fold_bn(const NetFile& nf, const std::string& conv, const std::string& bn
 struct BlockFold { Folded expand, dw, project; };
 BlockFold fold_block(const NetFile& nf, const std::string& prefix);
 
+// A NextViT transformer block (NTB, next_vit_official_modules.py:267-335) folded for the layer kernels: every 1x1 / linear layer as a
+// dense [cout][cin] Folded, BN folded in behind (patch_embed, projection, MHCA) or in front (norm1 into q / k / v, norm2 into mlp.conv1:
+// merge_pre_bn, next_vit_official_modules.py:21-62), MHCA's grouped 3x3 as a block-diagonal dense 3x3.  Widths: D = E_MHSA channels,
+// M = C - D (MHCA), H = the Mlp's hidden width.  Throws std::runtime_error naming the cause for what the layer path does not run:
+// head_dim != 32, sr_ratio > 1 (e_mhsa.norm present), the "simple" variant (no projection / MHCA) and missing or mis-shaped tensors.
+struct NtbFold {
+    int C = 0, D = 0, M = 0, H = 0;
+    Folded patch;       // [D][C]      conv1x1 + BN
+    Folded qkv;         // [3D][D]     q, k, v rows (norm1 folded in), bias
+    Folded proj;        // [D][D]      bias
+    Folded projection;  // [M][D]      conv1x1 + BN
+    Folded mhca;        // [M][M][3][3] block-diagonal grouped 3x3 + BN
+    Folded mhca_proj;   // [M][M]      no bias
+    Folded mlp1;        // [H][C]      norm2 folded in, bias
+    Folded mlp2;        // [C][H]      bias
+    double macs = 0;    // per position, the attention core included
+};
+NtbFold fold_ntb(const NetFile& nf, const std::string& prefix, int C);
+
 uint8_t to_e4m3(double v);          // OCP e4m3fn, round to nearest even, clamps at +-448
 uint8_t to_e5m2(float f);           // e5m2 ("bf8"), round to nearest even, saturating
 double row_scale_pow2(double max_abs);

@@ -29,7 +29,7 @@ namespace {
 // the float16x3 forward's value head: false = conv GEMM + FC GEMM + value_final (three launches), true = value_head_kernel (one)
 constexpr bool kX3ValueHeadOneLaunch = true;
 
-enum class OpKind { PlanesToAct, Conv, Depthwise, SE, ValueHead, Softmax, Block, ValueFinal, SEGate, Tower, Head, Stem, ResTower, Forward, TowerX3, BlockX3Split, X3SplitFinish, HeadsSmall };
+enum class OpKind { PlanesToAct, Conv, Depthwise, SE, ValueHead, Softmax, Block, ValueFinal, SEGate, Tower, Head, Stem, ResTower, Forward, TowerX3, BlockX3Split, X3SplitFinish, HeadsSmall, Attention };
 
 struct Op {
     OpKind kind;
@@ -297,7 +297,8 @@ enum class Family {
     X3Tower,   // float16x3 / float16p8: a run of 3x3 or of 5x5 blocks in one launch (x3.hip: tower_x3_kernel, tower_p8_kernel)
     X3Split,   // float16x3 / float16p8 at small batches: a 3x3 block per launch over several workgroups per board (block_x3_split_kernel)
     Fused,     // one launch per block (kernels.hip: block_kernel; x3.hip: block_x3_kernel)
-    Layers     // expand, depthwise and project as three layer launches
+    Layers,    // expand, depthwise and project as three layer launches
+    Transformer   // a NextViT transformer block: conv GEMMs and the attention kernel (Builder::transformer_block)
 };
 struct BlockPlan {
     Family family;
@@ -315,6 +316,8 @@ template <typename T> struct RiseNet::Builder {
     // the model
     int B = 0, cin = 0, C = 0, cv = 0, fc = 0, cp = 0, n_labels = 0, cin_pad = 0;
     bool wdl = false, policy_map = true, dense_blocks = false, a0_blocks = false, dense_se = false;
+    bool transformers = false;        // some block is an NTB: every block and both heads run on the layer-granular kernels
+    std::vector<bool> ntb;            // per block: a NextViT transformer block (model file: use_transformers)
     std::vector<std::string> se_types;
     std::vector<int> cops, ks;
     // the paths that hold for the whole net
@@ -342,7 +345,7 @@ template <typename T> struct RiseNet::Builder {
     Builder(RiseNet& n, const NetFile& file) : net(n), im(*n.impl_), nf(file), prec(n.prec_), dev(n.dev_) {}
     void read_model();
     BlockPlan plan(size_t i) const;
-    bool block_fused(int k) const { return prec.fused && C == 256 && !(prec.x3() && k != 3); }   // float16x3 has a fused kernel for 3x3 blocks only
+    bool block_fused(int k) const { return prec.fused && C == 256 && !transformers && !(prec.x3() && k != 3); }   // float16x3 has a fused kernel for 3x3 blocks only
     void upload_dense(const void*& wpk, const void*& wpk_lo, const Folded& fd, int co, int ci, int k, int co_pad, int ci_pad);
     void set_conv_weights(ConvArgs& c, const Folded& fd, int co, int ci, int k, int co_pad, int ci_pad, bool p8 = false);
     ConvArgs& conv_op(const Folded& fd, const void* x, void* out, int ci, int ci_pad, int co, int k, int relu, bool p8 = false);
@@ -354,6 +357,7 @@ template <typename T> struct RiseNet::Builder {
     void dense_tower();
     void dense_layer_blocks();
     void bottleneck_blocks();
+    void transformer_block(size_t i);
     void flush_tower();
     void flush_x3_run();
     void one_launch_head();
@@ -388,7 +392,10 @@ template <typename T> void RiseNet::Builder<T>::read_model() {
     // layer kernels (conv GEMM + SE kernel), not on the one-launch dense tower
     if (dense_blocks)
         for (const std::string& t : se_types) dense_se |= !(t == "none" || t.empty());
-    if (C % 64 != 0 || C > 512) throw std::runtime_error("channels must be a multiple of 64 and <= 512");
+    // (every kernel specialised for a width needs C = 256; the mobile-bottleneck layer path takes any multiple of 32, AlphaVile's 224 among
+    // them -- the dense families keep the multiples of 64 they are tested at)
+    if (dense_blocks && (C % 64 != 0 || C > 512)) throw std::runtime_error("channels must be a multiple of 64 and <= 512");
+    if (C % 32 != 0 || C > 512) throw std::runtime_error("channels must be a multiple of 32 and <= 512");
     if (fc > 256 && fc % 256 != 0) throw std::runtime_error("unsupported value_fc_size");
 
     net.design_.nb_input_channels = cin;
@@ -415,11 +422,26 @@ template <typename T> void RiseNet::Builder<T>::read_model() {
         cop_max = std::max(cop_max, c);
         cop_run += cexp;
     }
+    // NextViT transformer blocks (RiseV3(use_transformers), AlphaVile): the scratch tiles e / f also hold q|k|v (3 D < 3 C channels) and
+    // the Mlp's hidden layer
+    const std::vector<std::string> tr_list = nf.list("use_transformers");
+    if (!tr_list.empty() && tr_list.size() != kernels.size()) throw std::runtime_error("use_transformers/kernels mismatch in model file");
+    ntb.assign(kernels.size(), false);
+    for (size_t i = 0; i < tr_list.size(); ++i) {
+        const std::string& t = tr_list[i];
+        ntb[i] = !(t == "0" || t == "none" || t == "False" || t == "false" || t.empty());
+        if (!ntb[i]) continue;
+        if (dense_blocks) throw std::runtime_error("transformer blocks are supported in RiseV3 mobile-bottleneck nets only");
+        transformers = true;
+        const std::string p = "body_spatial." + std::to_string(i + 1) + ".mlp.conv1.weight";
+        cop_max = std::max(cop_max, 3 * C);
+        if (nf.has(p)) cop_max = std::max(cop_max, int(nf.get(p).shape[0]));
+    }
 
-    tower_ok = prec.tower && prec.fused && kHalf && C == 256 && !dense_se;
+    tower_ok = prec.tower && prec.fused && kHalf && C == 256 && !dense_se && !transformers;
     if (prec.fp8_tower() && (!tower_ok || dense_blocks))
         throw std::runtime_error("Precision fp8 runs on the one-launch bottleneck tower only (256-channel RISE nets): use float16 for this model");
-    x3_tower = prec.x3() && prec.tower && prec.fused && C == 256;
+    x3_tower = prec.x3() && prec.tower && prec.fused && C == 256 && !transformers;
     x3_split = x3_tower && prec.board_split && B <= kBoardSplitMaxBatch;
     // value heads with fewer than 8 channels (AlphaZeroResnet: 4) run as 8 with zero rows: ReLU(0) = 0 meets zero FC weights
     head_ok = tower_ok && policy_map && cv >= 1 && cv <= 8 && cp <= 96 && (wdl || fc == 256);
@@ -441,6 +463,7 @@ template <typename T> void RiseNet::Builder<T>::read_model() {
 // the one place that decides which family runs bottleneck block i and where its SE gate is computed
 template <typename T> BlockPlan RiseNet::Builder<T>::plan(size_t i) const {
     const int k = ks[i];
+    if (ntb[i]) return {Family::Transformer, false};
     if (tower_ok) return {Family::Tower, i > 0};          // 3x3 and 5x5 blocks in one run; the run's first gate comes from an SE launch
     if (x3_tower) {
         // the 5x5 blocks (RISEv3.3) run in tower launches of their own (tower_*_kernel<5>); small batches run 3x3 blocks split-board (float16x3
@@ -539,7 +562,7 @@ template <typename T> void RiseNet::Builder<T>::add_se(Op op, bool consumer_fuse
 
 template <typename T> void RiseNet::Builder<T>::stem() {
     const int cin_pad16 = std::max(48, round_up(cin, 16));
-    if (prec.tower && prec.fused && kHalf && C == 256 && cin_pad16 <= 96) {
+    if (prec.tower && prec.fused && kHalf && C == 256 && cin_pad16 <= 96 && !transformers) {
         // stem kernel: planes -> conv3x3 + BN + ReLU -> NHWC f16 in one launch (stem.hip)
         const StemStreams ss = pack_stem(fold_bn(nf, "body_spatial.0.body.0", "body_spatial.0.body.1"), cin, cin_pad16);
         Op op;
@@ -640,6 +663,10 @@ template <typename T> void RiseNet::Builder<T>::bottleneck_blocks() {
         const std::string p = "body_spatial." + std::to_string(i + 1);
         const int cop = cops[i], k = ks[i];
         const BlockPlan bp = plan(i);
+        if (bp.family == Family::Transformer) {
+            transformer_block(i);
+            continue;
+        }
         const bool x3_family = bp.family == Family::X3Tower || bp.family == Family::X3Split;
         if (!x3_blocks.empty() && x3_run_ks != k) flush_x3_run();
         TowerBlockDesc td{};
@@ -745,6 +772,53 @@ template <typename T> void RiseNet::Builder<T>::bottleneck_blocks() {
     }
     flush_tower();
     flush_x3_run();
+}
+
+// NTB (next_vit_official_modules.py:267-335) on the layer kernels.  The block's C-wide tile xs (= nxt) holds the E_MHSA part in channels
+// [0, D) and the MHCA part in [D, C): the concat is where the convs write (ConvArgs::cout_ld = C) and read (ConvArgs::x_ld = C), no copy.
+//   patch_embed    cur -> xs[0, D)                   conv1x1 + BN
+//   q | k | v      xs[0, D) -> e [3D]                one GEMM, norm1 folded in, bias
+//   attention      e -> f [D]                        attention.hip
+//   proj           f -> xs[0, D), + xs[0, D)         bias; the residual is the patch-embed output (in place: each element is read and
+//                                                    written by the same lane)
+//   projection     xs[0, D) -> xs[D, C)              conv1x1 + BN: u
+//   MHCA           xs[D, C) -> f [M]                 block-diagonal 3x3 + BN + ReLU
+//                  f -> xs[D, C), + u                conv1x1
+//   Mlp            xs -> e [H] -> cur, + xs          norm2 folded into conv1; ReLU; conv2 (the block input is dead by then)
+template <typename T> void RiseNet::Builder<T>::transformer_block(size_t i) {
+    const NtbFold n = fold_ntb(nf, "body_spatial." + std::to_string(i + 1), C);
+    const int D = n.D, M = n.M, H = n.H;
+    T* xs = nxt;
+    conv_op(n.patch, cur, xs, C, C, D, 1, 0).cout_ld = C;
+    conv_op(n.qkv, xs, e, D, D, 3 * D, 1, 0).x_ld = C;
+    {
+        Op op;
+        op.kind = OpKind::Attention;
+        op.x = e;
+        op.y = f;
+        op.C = D;
+        im.ops.push_back(op);
+    }
+    {
+        ConvArgs& c = conv_op(n.proj, f, xs, D, D, D, 1, 0);
+        c.resid = xs;
+        c.cout_ld = C;
+    }
+    {
+        ConvArgs& c = conv_op(n.projection, xs, xs + D, D, D, M, 1, 0);
+        c.x_ld = C;
+        c.cout_ld = C;
+    }
+    conv_op(n.mhca, xs + D, f, M, M, M, 3, 1).x_ld = C;
+    {
+        ConvArgs& c = conv_op(n.mhca_proj, f, xs + D, M, M, M, 1, 0);
+        c.resid = xs + D;
+        c.cout_ld = C;
+    }
+    conv_op(n.mlp1, xs, e, C, C, H, 1, 1);
+    conv_op(n.mlp2, e, cur, H, H, C, 1, 0).resid = xs;
+    macs += n.macs;
+    prod_op = -1;
 }
 
 template <typename T> void RiseNet::Builder<T>::flush_tower() {
@@ -1211,6 +1285,11 @@ template <typename T> void RiseNet::launch_op(int i, hipStream_t s, const IoOver
             launch_forward(st, op.tw, h, s);
             break;
         }
+        case OpKind::Attention: {
+            AttentionArgs at{op.x, op.y, B, op.C, prec_.fp16() ? 0 : prec_.x3() ? 2 : 1};
+            launch_attention(at, s);
+            break;
+        }
         case OpKind::SEGate:
             launch_se_gate(static_cast<const float*>(op.x), static_cast<float*>(op.y), op.se_kind, op.w0, op.w1, op.b0, B, op.C, s);
             break;
@@ -1246,6 +1325,7 @@ const char* RiseNet::op_name(int i) const {
         case OpKind::BlockX3Split: return "block_x3_split";
         case OpKind::X3SplitFinish: return "x3_split_finish";
         case OpKind::HeadsSmall: return "heads_small";
+        case OpKind::Attention: return "attention";
     }
     return "?";
 }

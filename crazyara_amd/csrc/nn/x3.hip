@@ -264,7 +264,8 @@ __device__ __forceinline__ void conv_gemm_x3_body(const ConvArgs& a, char* smem,
     bool active[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) active[m] = (co_tile0 + m) * 16 < a.cout_pad;
-    const float* xb = reinterpret_cast<const float*>(a.x) + size_t(b) * kSquares * a.cin;
+    const int x_ld = a.x_ld ? a.x_ld : a.cin;
+    const float* xb = reinterpret_cast<const float*>(a.x) + size_t(b) * kSquares * x_ld;
     const int nslab_ci = a.cin >> 5;
     const int nslab = KS * KS * nslab_ci;
     const half8 *wph[MT], *wpl[MT];
@@ -316,7 +317,7 @@ __device__ __forceinline__ void conv_gemm_x3_body(const ConvArgs& a, char* smem,
 #pragma unroll
                 for (int j = 0; j < 8; ++j) f[j] = 0.f;
             } else {
-                load8<float>(xb + size_t(r) * a.cin + kc0 + v * 8, f);
+                load8<float>(xb + size_t(r) * x_ld + kc0 + v * 8, f);
             }
             half8 h, l;
             split8(f, h, l);

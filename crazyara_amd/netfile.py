@@ -80,6 +80,13 @@ def export_rise(path: str, cfg, state_dict, input_version: str = "1.0", variant:
         conv_block=getattr(cfg, "conv_block", "mobile_bottlekneck_res_block"),
         select_policy_from_plane=int(getattr(cfg, "select_policy_from_plane", True)), n_labels=getattr(cfg, "n_labels", 2272),
     )
+    # AlphaVile nets (alpha_vile.py): which blocks are NextViT transformer blocks, and the C_op of every block (kernel_5_channel_ratio
+    # gives the 5x5 blocks widths the reader's default schedule does not know).  Written only for nets that have them.
+    use_transformers = getattr(cfg, "use_transformers", None)
+    if use_transformers and any(use_transformers):
+        meta["use_transformers"] = [int(bool(t)) for t in use_transformers]
+    if use_transformers and any(use_transformers) or getattr(cfg, "kernel_5_channel_ratio", None) is not None:
+        meta["channels_operating"] = list(cfg.channels_operating())
     tensors = {}
     for k, v in state_dict.items():
         if k.endswith("num_batches_tracked"):

@@ -38,6 +38,11 @@ class RiseConfig:
     # False = flat labels: BN + ReLU on the planes, then Linear(P*64 -> n_labels)
     select_policy_from_plane: bool = True
     n_labels: int = 2272
+    # RiseV3(use_transformers=...): use_transformers[i] makes block i a NextViT transformer block (NTB, next_vit_official_modules.py:267-335)
+    # instead of a bottleneck; None = none (AlphaVile nets, alpha_vile.py)
+    use_transformers: Optional[List[bool]] = None
+    # RiseV3(kernel_5_channel_ratio=...): the 5x5 blocks' C_op is int(C_op * ratio + 0.5) instead of C_op - 32 * (idx // 2)
+    kernel_5_channel_ratio: Optional[float] = None
 
     @property
     def dense_blocks(self) -> bool:
@@ -49,13 +54,25 @@ class RiseConfig:
         return "body" if self.conv_block == "a0_res_block" else "body_spatial"
 
     def channels_operating(self) -> List[int]:
-        """C_op per block, rise_mobile_v3.py:36-78 (kernel_5_channel_ratio=None branch)."""
+        """C_op per block, rise_mobile_v3.py:36-78 (_get_res_blocks, both kernel_5_channel_ratio branches)."""
         out = []
         c = self.channels_operating_init
         for idx, k in enumerate(self.kernels):
-            out.append(c - 32 * (idx // 2) if k == 5 else c)
+            if k != 5:
+                out.append(c)
+            elif self.kernel_5_channel_ratio is None:
+                out.append(c - 32 * (idx // 2))
+            else:
+                out.append(int(c * self.kernel_5_channel_ratio + 0.5))
             c += self.channel_expansion
         return out
+
+    def transformer(self, i: int) -> bool:
+        return bool(self.use_transformers and self.use_transformers[i])
+
+    @property
+    def has_transformers(self) -> bool:
+        return any(self.transformer(i) for i in range(len(self.kernels)))
 
     @property
     def nb_policy(self) -> int:
@@ -113,6 +130,47 @@ def alpha_zero_config(n_blocks: int = 19, nb_input_channels: int = 34, channels_
                       name=f"alphazero-{n_blocks}" + ("-se" if use_se else ""))
 
 
+def make_divisible(v, divisor: int = 32) -> int:
+    """next_vit_official_modules.py:_make_divisible (min_value = divisor)"""
+    new_v = max(divisor, int(v + divisor / 2) // divisor * divisor)
+    return new_v + divisor if new_v < 0.9 * v else new_v
+
+
+def ntb_widths(channels: int):
+    """NTB(channels, channels) with its defaults (mix_block_ratio 0.75, mlp_ratio 2, head_dim 32): (D, M, hidden) -- the E_MHSA width,
+    the MHCA width (channels - D) and the Mlp's hidden width."""
+    d = make_divisible(int(channels * 0.75), 32)
+    return d, channels - d, make_divisible(channels * 2, 32)
+
+
+_ALPHA_VILE_K5 = {"tiny": (1, 2, 6, 7, 8, 9, 10), "small": (0, 4, 5, 6, 10, 11, 13, 15, 17, 20),
+                  "normal": (0, 4, 5, 7, 10, 12, 15, 16, 20, 21, 22, 23, 24, 25),
+                  "large": (1, 6, 7, 9, 10, 14, 18, 19, 23, 25, 26, 27, 28, 29, 33, 34, 35)}
+
+
+def alpha_vile_config(size: str = "normal", nb_input_channels: int = 52, channels_policy_head: int = 76, wdlp: bool = False) -> RiseConfig:
+    """AlphaVile as get_alpha_vile_model builds it (alpha_vile.py:14-158): RiseV3 with mobile bottlenecks, one or two NTBs, no SE."""
+    if size not in _ALPHA_VILE_K5:
+        raise ValueError(f"unknown AlphaVile size '{size}' (tiny | small | normal | large)")
+    channels = {"tiny": 192, "small": 192, "normal": 224, "large": 224}[size]
+    depth = {"tiny": 15, "small": 22, "normal": 26, "large": 37}[size]
+    nb_transformers = 2 if size in ("normal", "large") else 1
+    expansion_ratio = 2
+    ratio = (int(((channels * expansion_ratio * 0.68) / 32) + 0.5) * 32) / (channels * expansion_ratio)
+    kernels = [3] * depth
+    for i in _ALPHA_VILE_K5[size]:
+        kernels[i] = 5
+    use_transformers = [False] * depth
+    block_size = depth // (nb_transformers + 1)
+    for idx in range(depth % block_size + 2 * block_size - 1, depth, block_size):
+        use_transformers[idx] = True
+    return RiseConfig(nb_input_channels=nb_input_channels, channels=channels, channels_operating_init=channels * expansion_ratio,
+                      channel_expansion=0, kernels=kernels, se_types=[None] * depth, channels_value_head=8, value_fc_size=channels,
+                      channels_policy_head=channels_policy_head, use_wdl=wdlp, use_plys_to_end=wdlp,
+                      use_transformers=use_transformers, kernel_5_channel_ratio=ratio,
+                      name=f"alphavile-{size}" + ("-wdlp" if wdlp else ""))
+
+
 def eca_kernel(channels: int, gamma: int = 2, b: int = 1) -> int:
     t = int(abs((math.log(channels, 2) + b) / gamma))
     return t if t % 2 else t + 1
@@ -167,6 +225,34 @@ def make_state_dict(cfg: RiseConfig, seed: int = 0, stress: bool = True) -> Dict
         if bias:
             sd[name + ".bias"] = torch.tensor(b, dtype=torch.float32)
 
+    def conv_bias(name, cout, fan_in):
+        b = rng.normal(0, 0.1, cout) if stress else rng.uniform(-1.0 / math.sqrt(fan_in), 1.0 / math.sqrt(fan_in), cout)
+        sd[name + ".bias"] = torch.tensor(b, dtype=torch.float32)
+
+    def ntb(p, nblk):
+        """NTB(C, C) (next_vit_official_modules.py:267-335), sr_ratio 1: the reference's parameter names.  Stress init: q / k at twice
+        the variance-preserving scale, so that the softmax over the 64 squares is neither flat nor one-hot; the three branches that add
+        into the stream (proj, MHCA projection, mlp.conv2) scaled like a bottleneck's last BN."""
+        D, M, H = ntb_widths(C)
+        out = (1.0 / math.sqrt(nblk)) if stress else 1.0
+        conv(p + ".patch_embed.conv", D, C, 1, gain=0.5)      # (no shortcut around patch_embed: keep the stream's scale)
+        bn(p + ".patch_embed.norm", D)
+        bn(p + ".norm1", D)
+        linear(p + ".e_mhsa.q", D, D, gain=math.sqrt(2.0))
+        linear(p + ".e_mhsa.k", D, D, gain=math.sqrt(2.0))
+        linear(p + ".e_mhsa.v", D, D)
+        linear(p + ".e_mhsa.proj", D, D, gain=out)
+        conv(p + ".projection.conv", M, D, 1)
+        bn(p + ".projection.norm", M)
+        conv(p + ".mhca.group_conv3x3", M, 32, 3)
+        bn(p + ".mhca.norm", M)
+        conv(p + ".mhca.projection", M, M, 1, gain=out)
+        bn(p + ".norm2", C)
+        conv(p + ".mlp.conv1", H, C, 1)
+        conv_bias(p + ".mlp.conv1", H, C)
+        conv(p + ".mlp.conv2", C, H, 1, gain=0.5 * out)
+        conv_bias(p + ".mlp.conv2", C, H)
+
     C = cfg.channels
     pre = cfg.key_prefix
     conv(pre + ".0.body.0", C, cfg.nb_input_channels, 3, gain=2.0)
@@ -174,6 +260,9 @@ def make_state_dict(cfg: RiseConfig, seed: int = 0, stress: bool = True) -> Dict
     nblk = len(cfg.kernels)
     for i, (k, cop, se) in enumerate(zip(cfg.kernels, cfg.channels_operating(), cfg.se_types)):
         p = f"{pre}.{i + 1}"
+        if cfg.transformer(i):
+            ntb(p, nblk)
+            continue
         if cfg.dense_blocks:
             if se in ("ca_se", "se"):
                 linear(p + ".se.fc.0", C // 2, C, bias=False)
@@ -205,17 +294,19 @@ def make_state_dict(cfg: RiseConfig, seed: int = 0, stress: bool = True) -> Dict
         bn(p + ".body.7", C, out_scale=(1.0 / math.sqrt(nblk)) if stress else 1.0)
     conv("policy_head.body.0", C, C, 3)
     bn("policy_head.body.1", C)
-    conv("policy_head.body.3", cfg.channels_policy_head, C, 3, gain=0.35 if cfg.dense_blocks else 1.0)   # logits O(1) either way
+    conv("policy_head.body.3", cfg.channels_policy_head, C, 3, gain=0.35 if cfg.dense_blocks or cfg.has_transformers else 1.0)   # logits O(1) either way
     if not cfg.select_policy_from_plane:
         bn("policy_head.body2.0", cfg.channels_policy_head)
         linear("policy_head.body3.0", cfg.n_labels, cfg.channels_policy_head * 64, gain=0.35)
     conv("value_head.body.0", cfg.channels_value_head, C, 1)
     bn("value_head.body.1", cfg.channels_value_head)
     nflat = 64 * cfg.channels_value_head
+    # (transformer nets: AlphaVile's deep trunks carry a larger stream into the heads; smaller head gains keep value and WDL logits O(0.3))
+    vg = 0.25 if cfg.has_transformers else 1.0
     if cfg.use_wdl:
-        linear("value_head.body_wdl.0", 3, nflat, gain=0.7)
+        linear("value_head.body_wdl.0", 3, nflat, gain=0.7 * vg)
     if cfg.use_plys_to_end:
-        linear("value_head.body_plys.0", 1, nflat, gain=0.7)
+        linear("value_head.body_plys.0", 1, nflat, gain=0.7 * vg)
     linear("value_head.body_final.0", cfg.value_fc_size, nflat)
-    linear("value_head.body_final.2", 1, cfg.value_fc_size, gain=0.5)
+    linear("value_head.body_final.2", 1, cfg.value_fc_size, gain=0.5 * vg)
     return sd

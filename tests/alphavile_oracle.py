@@ -1,0 +1,243 @@
+"""fp32 torch restatement of the AlphaVile forward (RiseV3 with NextViT transformer blocks) -- the test-side oracle of the NTB tests.
+
+Stem, bottleneck blocks and heads come from oracle.rise_oracle (read only); the NTB (next_vit_official_modules.py: NTB, E_MHSA, MHCA,
+Mlp, PatchEmbed) is restated here in eval mode with sr_ratio 1:
+
+    x = BN(conv1x1(x, C -> D))                            patch_embed
+    x = x + proj(softmax(q k^T / sqrt(32)) v)             E_MHSA on BN_norm1(x), heads of 32 channels, the 64 squares as tokens
+    u = BN(conv1x1(x, D -> M))                            projection
+    u = u + conv1x1(ReLU(BN(groupconv3x3(u))))            MHCA, groups = M / 32
+    x = cat(x, u)
+    x = x + conv2(ReLU(conv1(BN_norm2(x))))               Mlp
+"""
+import os
+import sys
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from crazyara_amd.rise_config import ntb_widths  # noqa: E402
+from oracle import rise_oracle as ro  # noqa: E402
+
+HEAD_DIM = 32
+
+
+def ntb(sd, p, x, uniform_attention=False):
+    """One NTB on x [B, C, 8, 8]; uniform_attention: every softmax row replaced by 1/64 (the non-degeneracy check)."""
+    C = x.shape[1]
+    D, M, _ = ntb_widths(C)
+    x = ro._bn(sd, p + ".patch_embed.norm", F.conv2d(x, sd[p + ".patch_embed.conv.weight"]))
+    B = x.shape[0]
+    t = ro._bn(sd, p + ".norm1", x).reshape(B, D, 64).transpose(1, 2)            # [B, 64 tokens, D]
+    q = F.linear(t, sd[p + ".e_mhsa.q.weight"], sd[p + ".e_mhsa.q.bias"])
+    k = F.linear(t, sd[p + ".e_mhsa.k.weight"], sd[p + ".e_mhsa.k.bias"])
+    v = F.linear(t, sd[p + ".e_mhsa.v.weight"], sd[p + ".e_mhsa.v.bias"])
+    nh = D // HEAD_DIM
+    q = q.reshape(B, 64, nh, HEAD_DIM).permute(0, 2, 1, 3)
+    k = k.reshape(B, 64, nh, HEAD_DIM).permute(0, 2, 3, 1)
+    v = v.reshape(B, 64, nh, HEAD_DIM).permute(0, 2, 1, 3)
+    attn = (q @ k) * HEAD_DIM ** -0.5
+    attn = torch.full_like(attn, 1.0 / 64) if uniform_attention else attn.softmax(dim=-1)
+    o = (attn @ v).transpose(1, 2).reshape(B, 64, D)
+    o = F.linear(o, sd[p + ".e_mhsa.proj.weight"], sd[p + ".e_mhsa.proj.bias"])
+    x = x + o.transpose(1, 2).reshape(B, D, 8, 8)
+    u = ro._bn(sd, p + ".projection.norm", F.conv2d(x, sd[p + ".projection.conv.weight"]))
+    g = F.relu(ro._bn(sd, p + ".mhca.norm", F.conv2d(u, sd[p + ".mhca.group_conv3x3.weight"], padding=1, groups=M // HEAD_DIM)))
+    u = u + F.conv2d(g, sd[p + ".mhca.projection.weight"])
+    x = torch.cat([x, u], dim=1)
+    h = F.relu(F.conv2d(ro._bn(sd, p + ".norm2", x), sd[p + ".mlp.conv1.weight"], sd[p + ".mlp.conv1.bias"]))
+    return x + F.conv2d(h, sd[p + ".mlp.conv2.weight"], sd[p + ".mlp.conv2.bias"])
+
+
+def _bottleneck(sd, p, se, k, h):
+    if se in ("ca_se", "se"):
+        y = F.relu(F.linear(h.mean(dim=(2, 3)), sd[p + ".se.fc.0.weight"]))
+        h = h * F.hardsigmoid(F.linear(y, sd[p + ".se.fc.2.weight"]))[:, :, None, None]
+    elif se == "eca_se":
+        w = sd[p + ".se.body.0.weight"]
+        y = F.conv1d(h.mean(dim=(2, 3))[:, :, None], w, sd[p + ".se.body.0.bias"], padding=w.shape[2] // 2)[:, :, 0]
+        h = h * F.hardsigmoid(y)[:, :, None, None]
+    t = F.relu(ro._bn(sd, p + ".body.1", F.conv2d(h, sd[p + ".body.0.weight"])))
+    t = F.relu(ro._bn(sd, p + ".body.4", F.conv2d(t, sd[p + ".body.3.weight"], padding=k // 2, groups=t.shape[1])))
+    return h + ro._bn(sd, p + ".body.7", F.conv2d(t, sd[p + ".body.6.weight"]))
+
+
+@torch.no_grad()
+def forward(cfg, sd, x, uniform_attention=False):
+    """(value [B, 1], policy logits [B, P*64], aux [B, 4] or None) of a RiseV3 net whose blocks may be NTBs.  x: [B, C, 8, 8]."""
+    x = x.to(torch.float32)
+    h = F.relu(ro._bn(sd, "body_spatial.0.body.1", F.conv2d(x, sd["body_spatial.0.body.0.weight"], padding=1)))
+    for i, (k, se) in enumerate(zip(cfg.kernels, cfg.se_types)):
+        p = f"body_spatial.{i + 1}"
+        h = ntb(sd, p, h, uniform_attention) if cfg.transformer(i) else _bottleneck(sd, p, se, k, h)
+    return ro._heads(cfg, sd, h)
+
+
+def predict(cfg, sd, x):
+    """NeuralNetAPI::predict contract: value, policy after the softmax, aux."""
+    value, pol, aux = forward(cfg, sd, x)
+    return value.reshape(-1), torch.softmax(pol, dim=1), aux
+
+
+def flops_per_position(cfg) -> float:
+    """2 * MACs per position: oracle.rise_oracle's count with each NTB's MACs in place of a bottleneck's (attention core included)."""
+    total = ro.flops_per_position(cfg)
+    C = cfg.channels
+    for i, (k, cop, se) in enumerate(zip(cfg.kernels, cfg.channels_operating(), cfg.se_types)):
+        if not cfg.transformer(i):
+            continue
+        total -= 2.0 * (64 * C * cop * 2 + 64 * cop * k * k)
+        D, M, H = ntb_widths(C)
+        macs = 64 * C * D                   # patch_embed
+        macs += 64 * D * 3 * D              # q, k, v
+        macs += 2 * 64 * 64 * D             # Q K^T and P V over all heads
+        macs += 64 * D * D                  # proj
+        macs += 64 * D * M                  # projection
+        macs += 64 * M * HEAD_DIM * 9       # MHCA grouped 3x3
+        macs += 64 * M * M                  # MHCA projection
+        macs += 2 * 64 * C * H              # Mlp
+        total += 2.0 * macs
+    return total
+
+
+def import_reference_alpha_vile():
+    """The reference's get_alpha_vile_model (timm and einops stubbed: DropPath is the identity in eval mode, and the NTB only uses
+    einops.rearrange for the two token reshapes)."""
+    import types
+    from oracle.make_golden import import_reference
+    import_reference()
+    if "einops" not in sys.modules:
+        try:
+            import einops  # noqa: F401
+        except ImportError:
+            def rearrange(t, pattern, **kw):
+                if pattern == "b c h w -> b (h w) c":
+                    return t.flatten(2).transpose(1, 2)
+                if pattern == "b (h w) c -> b c h w":
+                    h = kw["h"]
+                    return t.transpose(1, 2).reshape(t.shape[0], t.shape[2], h, t.shape[1] // h)
+                raise NotImplementedError(pattern)
+            mod = types.ModuleType("einops")
+            mod.rearrange = rearrange
+            sys.modules["einops"] = mod
+    from DeepCrazyhouse.src.domain.neural_net.architectures.pytorch.alpha_vile import get_alpha_vile_model
+    return get_alpha_vile_model
+
+
+def reference_alpha_vile(size, cfg):
+    """get_alpha_vile_model(args, size) in eval mode for the config's input / head shape."""
+    get_alpha_vile_model = import_reference_alpha_vile()
+
+    class Args:
+        input_shape = (cfg.nb_input_channels, 8, 8)
+        channels_policy_head = cfg.channels_policy_head
+        select_policy_from_plane = cfg.select_policy_from_plane
+        n_labels = cfg.n_labels
+        use_wdl = cfg.use_wdl
+        use_plys_to_end = cfg.use_plys_to_end
+        use_mlp_wdl_ply = False
+
+    return get_alpha_vile_model(Args, size).eval()
+
+
+# the golden cases: name -> (size, wdlp, seed); inputs are chess v3.0 planes (52 channels), batch 4
+CASES = {"alphavile-tiny": ("tiny", False, 31), "alphavile-normal": ("normal", False, 32), "alphavile-normal-wdlp": ("normal", True, 33)}
+GOLDEN_BATCH = 4
+
+
+def make_case(name, batch=GOLDEN_BATCH):
+    """(cfg, state dict, planes [batch, 52, 8, 8]) of a golden case: stress-initialised weights from (config, seed)."""
+    from crazyara_amd.rise_config import alpha_vile_config, make_state_dict
+    from tests import nn_cases
+    size, wdlp, seed = CASES[name]
+    cfg = alpha_vile_config(size, wdlp=wdlp)
+    sd = make_state_dict(cfg, seed=seed, stress=True)
+    return cfg, sd, nn_cases.synthetic_planes(batch, cfg.nb_input_channels, seed + 1000)
+
+
+# --------------------------------------------------------------------------------------------------------------
+# Precision float16 on the layer-granular kernels, emulated: which roundings the HIP path adds to the fp32 forward above.
+#   every conv / linear ... BN folded into the weights (behind, or in front for norm1 / norm2), weights and input rounded to f16, f32
+#                           accumulate, f32 bias, residual read as f16, output stored as f16
+#   depthwise ............. f16 input, f32 folded weights, f32 accumulate, f16 output
+#   SE .................... gate from the f16 tile in f32, gated tile stored as f16
+#   attention core ........ q, k, v as stored (f16), S in f32, softmax in f32, P rounded to f16, O stored as f16
+#   heads ................. oracle.rise_oracle._heads(sim_dtype=float16)
+# Not bit-exact (accumulation order differs): it says how large the error of f16 storage is on a given net, independent of the kernels.
+# --------------------------------------------------------------------------------------------------------------
+def _r(t):
+    return t.half().float()
+
+
+def _fold(sd, conv, bn):
+    w = sd[conv + ".weight"]
+    if bn is None:
+        return w, torch.zeros(w.shape[0])
+    s = sd[bn + ".weight"] / torch.sqrt(sd[bn + ".running_var"] + ro.BN_EPS)
+    return w * s.view(-1, *([1] * (w.dim() - 1))), sd[bn + ".bias"] - sd[bn + ".running_mean"] * s
+
+
+def _fold_pre(sd, w, b, bn):
+    """merge_pre_bn: W BN(x) + b with W [out][in]"""
+    s = sd[bn + ".weight"] / torch.sqrt(sd[bn + ".running_var"] + ro.BN_EPS)
+    return w * s.view(1, -1), b + w @ (sd[bn + ".bias"] - sd[bn + ".running_mean"] * s)
+
+
+def _conv16(x, w, b, padding=0, resid=None, relu=False):
+    y = F.conv2d(_r(x), _r(w), padding=padding) + b.view(1, -1, 1, 1)
+    if resid is not None:
+        y = y + _r(resid)
+    return _r(F.relu(y) if relu else y)
+
+
+def _ntb16(sd, p, x):
+    C = x.shape[1]
+    D, M, _ = ntb_widths(C)
+    B = x.shape[0]
+    xs = _conv16(x, *_fold(sd, p + ".patch_embed.conv", p + ".patch_embed.norm"))
+    ws, bs = zip(*[_fold_pre(sd, sd[f"{p}.e_mhsa.{n}.weight"], sd[f"{p}.e_mhsa.{n}.bias"], p + ".norm1") for n in "qkv"])
+    qkv = _conv16(xs, torch.cat(ws)[:, :, None, None], torch.cat(bs)).reshape(B, 3 * D, 64).transpose(1, 2)
+    nh = D // HEAD_DIM
+    q = qkv[..., :D].reshape(B, 64, nh, HEAD_DIM).permute(0, 2, 1, 3)
+    k = qkv[..., D:2 * D].reshape(B, 64, nh, HEAD_DIM).permute(0, 2, 3, 1)
+    v = qkv[..., 2 * D:].reshape(B, 64, nh, HEAD_DIM).permute(0, 2, 1, 3)
+    attn = _r(((q @ k) * HEAD_DIM ** -0.5).softmax(dim=-1))
+    o = _r((attn @ v).transpose(1, 2).reshape(B, 64, D)).transpose(1, 2).reshape(B, D, 8, 8)
+    xs = _conv16(o, sd[p + ".e_mhsa.proj.weight"][:, :, None, None], sd[p + ".e_mhsa.proj.bias"], resid=xs)
+    u = _conv16(xs, *_fold(sd, p + ".projection.conv", p + ".projection.norm"))
+    wg, bg = _fold(sd, p + ".mhca.group_conv3x3", p + ".mhca.norm")
+    g = _r(F.relu(F.conv2d(_r(u), _r(wg), padding=1, groups=M // HEAD_DIM) + bg.view(1, -1, 1, 1)))
+    u = _conv16(g, sd[p + ".mhca.projection.weight"], torch.zeros(M), resid=u)
+    x = torch.cat([xs, u], dim=1)
+    w1, b1 = _fold_pre(sd, sd[p + ".mlp.conv1.weight"][:, :, 0, 0], sd[p + ".mlp.conv1.bias"], p + ".norm2")
+    h = _conv16(x, w1[:, :, None, None], b1, relu=True)
+    return _conv16(h, sd[p + ".mlp.conv2.weight"], sd[p + ".mlp.conv2.bias"], resid=x)
+
+
+def _bottleneck16(sd, p, se, k, h):
+    if se is not None:
+        y = h.mean(dim=(2, 3))
+        if se in ("ca_se", "se"):
+            y = F.hardsigmoid(F.linear(F.relu(F.linear(y, sd[p + ".se.fc.0.weight"])), sd[p + ".se.fc.2.weight"]))
+        else:
+            w = sd[p + ".se.body.0.weight"]
+            y = F.hardsigmoid(F.conv1d(y[:, :, None], w, sd[p + ".se.body.0.bias"], padding=w.shape[2] // 2)[:, :, 0])
+        h = _r(h * y[:, :, None, None])
+    t = _conv16(h, *_fold(sd, p + ".body.0", p + ".body.1"), relu=True)
+    wd, bd = _fold(sd, p + ".body.3", p + ".body.4")
+    t = _r(F.relu(F.conv2d(t, wd, padding=k // 2, groups=t.shape[1]) + bd.view(1, -1, 1, 1)))
+    return _conv16(t, *_fold(sd, p + ".body.6", p + ".body.7"), resid=h)
+
+
+@torch.no_grad()
+def forward_f16(cfg, sd, x):
+    """The float16 layer path's roundings on the fp32 forward (see above): (value, logits, aux)."""
+    h = _conv16(x.to(torch.float32), *_fold(sd, "body_spatial.0.body.0", "body_spatial.0.body.1"), padding=1, relu=True)
+    for i, (k, se) in enumerate(zip(cfg.kernels, cfg.se_types)):
+        p = f"body_spatial.{i + 1}"
+        h = _ntb16(sd, p, h) if cfg.transformer(i) else _bottleneck16(sd, p, se, k, h)
+    return ro._heads(cfg, sd, h, torch.float16)
