@@ -315,6 +315,9 @@ private:
     bool is_linear(const Node& n) const { return n.op == "Gemm" || n.op == "MatMul"; }
     Linear linear(const Node& n) const;
     std::string se_gate(const std::string& x, const std::string& prefix, std::string& se_type, bool plain_sigmoid = false);
+    std::string transposes(const std::string& t, std::vector<int64_t>& perm, const Node* first = nullptr) const;
+    void check_views(const std::string& t, const std::vector<int64_t>& want, const std::string& p) const;
+    std::string transformer_block(const std::string& x, const std::string& p, int C, int& hidden);
 
     void put(const std::string& name, std::vector<int64_t> dims, std::vector<float> data) { out_.push_back({name, std::move(dims), std::move(data)}); }
     void put_conv_bn(const std::string& conv, const std::string& bn, const ConvUnit& u);
@@ -330,6 +333,8 @@ private:
     std::set<std::string> outputs_;
     std::map<std::string, std::string> alias_;
     std::map<std::string, std::vector<int>> cons_;
+    std::map<std::string, std::vector<int>> reshapes_;     // Reshape nodes by the (resolved) tensor they read
+    int64_t opset_ = 0;
     std::vector<Out> out_;
 };
 
@@ -340,6 +345,17 @@ void Importer::parse(Slice file) {
     while (r.next(f)) {
         if (f.num == 7 && f.wt == 2) graph = f.s;
         else if (f.num == 2 && f.wt == 2) producer_ = f.s.str();
+        else if (f.num == 8 && f.wt == 2) {
+            Reader o(f.s);
+            Field of;
+            std::string domain;
+            int64_t version = 0;
+            while (o.next(of)) {
+                if (of.num == 1 && of.wt == 2) domain = of.s.str();
+                else if (of.num == 2 && of.wt == 0) version = int64_t(of.v);
+            }
+            if (domain.empty() || domain == "ai.onnx") opset_ = version;
+        }
     }
     if (!graph.p) fail("no graph in the file (is this an ONNX model?)");
     Reader g(graph);
@@ -395,6 +411,7 @@ void Importer::index() {
             const std::string target = resolve(n.in[0]);
             if (target == n.out[0]) fail(n.label() + " aliases its own output");     // a damaged file: resolve() would never end
             alias_[n.out[0]] = target;
+            if (n.op == "Reshape") reshapes_[target].push_back(int(idx));
             continue;
         }
         for (const std::string& i : n.in) {
@@ -554,6 +571,266 @@ std::string Importer::se_gate(const std::string& x, const std::string& prefix, s
     return m.out[0];
 }
 
+// Follows a chain of Transpose nodes that starts at `t` (each the only reader of the tensor before it, each reading the previous one's
+// output directly: a Reshape between two Transposes ends the chain); `first`: the chain's first node, where `t` has other readers too.  perm = their composition, empty if `t` feeds no Transpose.
+// Returns the chain's output: a fused Transpose (onnx-simplifier) and the exporter's consecutive ones give the same perm.
+std::string Importer::transposes(const std::string& t, std::vector<int64_t>& perm, const Node* first) const {
+    perm.clear();
+    std::string cur = t;
+    for (int hop = 0; hop < 8; ++hop) {
+        const Node* tr = hop == 0 && first ? first : sole(cur, "Transpose");
+        if (!tr || tr->in.empty() || (hop > 0 && tr->in[0] != cur)) return cur;
+        const std::vector<int64_t>* pv = tr->ints_attr("perm");
+        if (!pv || pv->empty()) fail(tr->label() + ": needs an explicit perm");
+        if (hop == 0) perm = *pv;
+        else {
+            if (pv->size() != perm.size()) fail(tr->label() + ": perm rank differs from the Transpose before it");
+            std::vector<int64_t> c(perm.size());
+            for (size_t i = 0; i < c.size(); ++i) {
+                const int64_t j = (*pv)[i];
+                if (j < 0 || j >= int64_t(perm.size())) fail(tr->label() + ": perm out of range");
+                c[i] = perm[size_t(j)];
+            }
+            perm = std::move(c);
+        }
+        cur = tr->out[0];
+    }
+    fail("more than 8 Transpose nodes in a row at " + t);
+}
+
+// Every Reshape of `t` whose target is a constant must produce `want` (want[0], the batch axis, is free; one -1 may stand for any
+// other axis).  Computed targets (Shape / Gather / Concat chains of a dynamic-batch file) are shape plumbing and are not checked.
+void Importer::check_views(const std::string& t, const std::vector<int64_t>& want, const std::string& p) const {
+    auto it = reshapes_.find(resolve(t));
+    if (it == reshapes_.end()) return;
+    for (int idx : it->second) {
+        const Node& n = nodes_[size_t(idx)];
+        const Tensor* s = n.in.size() > 1 ? init(n.in[1]) : nullptr;
+        if (!s) continue;
+        bool ok = s->i.size() == want.size();
+        int wild = 0;
+        for (size_t i = 1; ok && i < want.size(); ++i) {
+            if (s->i[i] == -1) ++wild;
+            else ok = s->i[i] == want[i];
+        }
+        if (ok && wild <= 1) continue;
+        std::string got, exp = "B";
+        for (int64_t d : s->i) got += (got.empty() ? "" : ",") + std::to_string(d);
+        for (size_t i = 1; i < want.size(); ++i) exp += "," + std::to_string(want[i]);
+        fail("transformer block " + p + ": " + n.label() + " reshapes to [" + got + "], expected [" + exp +
+             "] (heads of 32 channels over the 64 squares)");
+    }
+}
+
+// NextViT transformer block (NTB, next_vit_official_modules.py:267-335) as the reference exports it after merge_bn(): norm1 / norm2 are
+// folded into q / k / v and mlp.conv1, so the graph holds no norm nodes.
+//   x -> conv1x1+BN (patch_embed) = p;  p -> Transpose(0,2,3,1) -> [B,64,D] = t
+//   t -> Linear q / k / v -> [B,64,h,32] -> Transpose (0,2,1,3) / (0,2,3,1) / (0,2,1,3)
+//   softmax((q @ kT) * s, axis -1) @ v -> Transpose(0,2,1,3) -> [B,64,D] -> Linear proj -> [B,8,8,D] -> Transpose(0,3,1,2) = a
+//   x1 = p + a;  r = conv1x1+BN(x1) (projection);  x2 = r + conv1x1(ReLU(groupconv3x3+BN(r)))  (MHCA)
+//   xc = Concat(x1, x2);  out = xc + conv1x1(ReLU(conv1x1(xc)))  (Mlp)
+// Matched by structure only (onnx-simplifier renames nodes).  Writes the tensors fold_ntb (pack.cpp) reads; hidden = the Mlp width.
+std::string Importer::transformer_block(const std::string& x, const std::string& p, int C, int& hidden) {
+    auto bad = [&](const std::string& m) { fail("transformer block " + p + ": " + m); };
+    auto same = [&](const std::string& a, const std::string& b) { return resolve(a) == resolve(b); };
+    auto joins = [&](const Node& add, const std::string& a, const std::string& b) {
+        return add.in.size() == 2 && ((same(add.in[0], a) && same(add.in[1], b)) || (same(add.in[0], b) && same(add.in[1], a)));
+    };
+    auto relu_after = [&](const ConvUnit& u, const char* what) {
+        if (u.relu) return;
+        for (int i : cons(u.out))
+            if (nodes_[size_t(i)].op == "HardSwish" || nodes_[size_t(i)].op == "HardSigmoid") bad(std::string(what) + ": hard-swish is not supported, only ReLU");
+        bad(std::string(what) + " must be followed by ReLU");
+    };
+    const std::vector<int64_t> q_perm{0, 2, 1, 3}, k_perm{0, 2, 3, 1}, tok_perm{0, 2, 3, 1}, board_perm{0, 3, 1, 2};
+    std::vector<int64_t> perm;
+
+    // ---- patch_embed, tokens ----
+    const ConvUnit pe = conv_unit(cons(x)[0]);
+    if (pe.k != 1 || pe.group != 1 || pe.cin_g != C || pe.relu) bad("patch_embed must be a conv1x1 + BN on the block input");
+    const int D = pe.cout, M = C - D;
+    if (D % 32 != 0 || M <= 0 || M % 32 != 0)
+        bad("E_MHSA width " + std::to_string(D) + " of " + std::to_string(C) + " channels is not a head_dim-32 split (both parts must be multiples of 32)");
+    const std::vector<int>& pc = cons(pe.out);
+    const int tr0 = pick(pc, "Transpose"), add1 = pick(pc, "Add");
+    if (pc.size() != 2 || tr0 < 0 || add1 < 0) bad("patch_embed must feed the token Transpose and the attention's residual Add");
+    const std::string tok = transposes(pe.out, perm, &nodes_[size_t(tr0)]);
+    if (perm != tok_perm) bad("the tokens must be the patch_embed output under Transpose(0,2,3,1) ('b c h w -> b (h w) c')");
+    check_views(tok, {0, 64, D}, p);
+
+    // ---- q, k, v ----
+    const std::vector<int> tc = cons(tok);
+    int n_lin = 0;
+    for (int i : tc) n_lin += is_linear(nodes_[size_t(i)]);
+    if (tc.size() != 3 || n_lin != 3) {
+        for (int i : tc) {
+            const std::string& op = nodes_[size_t(i)].op;
+            if (op == "Transpose" || op == "AveragePool" || op == "ReduceMean" || op == "GlobalAveragePool")
+                bad("E_MHSA with sr_ratio > 1 (pooled k / v) is not supported");
+        }
+        bad("the tokens must feed exactly the q, k and v layers");
+    }
+    Linear lin[3];
+    std::vector<int64_t> perms[3];
+    std::string outs[3];
+    const Node* mm[3];
+    for (int j = 0; j < 3; ++j) {
+        lin[j] = linear(nodes_[size_t(tc[size_t(j)])]);
+        if (lin[j].nin != D || lin[j].nout != D || !lin[j].has_bias) bad("q, k and v must be Linear(D, D) layers with bias");
+        check_views(lin[j].out, {0, 64, D / 32, 32}, p);
+        outs[j] = transposes(lin[j].out, perms[j]);
+        mm[j] = sole(outs[j], "MatMul");
+        if (!mm[j] || mm[j]->in.size() != 2) bad("q, k and v must each feed one attention MatMul");
+    }
+    int qi = -1, ki = -1, vi = -1;
+    for (int a = 0; a < 3 && qi < 0; ++a)
+        for (int b = a + 1; b < 3 && qi < 0; ++b)
+            if (mm[a] == mm[b]) {
+                vi = 3 - a - b;
+                qi = same(mm[a]->in[0], outs[a]) ? a : b;
+                ki = qi == a ? b : a;
+            }
+    if (qi < 0) bad("no MatMul of two of q, k, v (the attention scores)");
+    const Node* S = mm[qi];
+    if (!same(S->in[0], outs[qi]) || !same(S->in[1], outs[ki])) bad("the attention scores must be one MatMul of q and k");
+    if (perms[qi] == k_perm && perms[ki] == q_perm) bad("the attention scores MatMul has its operands in the wrong order (expected q @ k^T)");
+    if (perms[qi] == q_perm && perms[ki] == q_perm) bad("k is not transposed against q (k needs Transpose(0,2,3,1), q Transpose(0,2,1,3))");
+    if (perms[qi] != q_perm || perms[ki] != k_perm || perms[vi] != q_perm)
+        bad("q, k, v must be split into heads by Transpose (0,2,1,3), (0,2,3,1), (0,2,1,3)");
+
+    // ---- scale, softmax, attention @ v ----
+    std::string st = S->out[0];
+    double scale = 1.0;
+    bool std_scale = false;                   // exactly 32^-0.5: q's tensors stay bit-identical (the kernel applies 1/sqrt(32) itself)
+    auto scalar = [&](const Node& n, const std::string& other) -> const Tensor* {
+        for (const std::string& i : n.in)
+            if (!same(i, other)) {
+                const Tensor* t = init(i);
+                return t && t->f.size() == 1 ? t : nullptr;
+            }
+        return nullptr;
+    };
+    if (const Node* mul = sole(st, "Mul")) {
+        const Tensor* c = scalar(*mul, st);
+        if (!c || mul->in.size() != 2) bad("the attention scale must be a Mul by a scalar constant");
+        scale = c->f[0];
+        std_scale = c->f[0] == float(1.0 / std::sqrt(32.0));
+        st = mul->out[0];
+    } else if (const Node* dv = sole(st, "Div")) {
+        const Tensor* c = dv->in.size() == 2 && same(dv->in[0], st) ? init(dv->in[1]) : nullptr;
+        if (!c || c->f.size() != 1) bad("the attention scale must be a Div by a scalar constant");
+        scale = 1.0 / double(c->f[0]);
+        std_scale = c->f[0] == float(std::sqrt(32.0));
+        st = dv->out[0];
+    }
+    if (!std::isfinite(scale) || scale == 0.0) bad("the attention scale must be finite and non-zero");
+    const Node* sm = sole(st, "Softmax");
+    if (!sm) bad("the attention scores must feed one Softmax");
+    const int64_t ax = sm->int_attr("axis", opset_ > 0 && opset_ < 13 ? 1 : -1);
+    if (ax != -1 && ax != 3) bad("Softmax over axis " + std::to_string(ax) + "; the attention normalises over the keys (axis -1 or 3)");
+    const Node* O = sole(sm->out[0], "MatMul");
+    if (!O || O->in.size() != 2 || mm[vi] != O) bad("the attention weights must feed one MatMul with v");
+    if (!same(O->in[0], sm->out[0]) || !same(O->in[1], outs[vi])) bad("the MatMul of attention weights and v has its operands in the wrong order (expected softmax(.) @ v)");
+    const std::string o = transposes(O->out[0], perm);
+    if (perm != q_perm) bad("the heads must be merged by Transpose(0,2,1,3)");
+    check_views(o, {0, 64, D}, p);
+    const std::vector<int>& oc = cons(o);
+    if (oc.size() != 1 || !is_linear(nodes_[size_t(oc[0])])) bad("the merged heads must feed the proj Linear");
+    const Linear proj = linear(nodes_[size_t(oc[0])]);
+    if (proj.nin != D || proj.nout != D || !proj.has_bias) bad("proj must be a Linear(D, D) with bias");
+    check_views(proj.out, {0, 8, 8, D}, p);
+    const std::string a = transposes(proj.out, perm);
+    if (perm != board_perm) bad("the attention output must return to the board by Transpose(0,3,1,2) ('b (h w) c -> b c h w')");
+    const Node& an = nodes_[size_t(add1)];
+    if (!joins(an, pe.out, a) || cons(a).size() != 1) bad("the attention output must join the patch_embed output in one Add");
+    const std::string x1 = an.out[0];
+
+    // ---- projection, MHCA, Concat ----
+    const std::vector<int>& x1c = cons(x1);
+    const int prj = pick(x1c, "Conv"), cat = pick(x1c, "Concat");
+    if (x1c.size() != 2 || prj < 0 || cat < 0) bad("the E_MHSA output must feed the projection conv1x1 and the Concat");
+    const ConvUnit pr = conv_unit(prj);
+    if (pr.k != 1 || pr.group != 1 || pr.cin_g != D || pr.cout != M || pr.relu) bad("projection must be a conv1x1 + BN from D to C - D channels");
+    const std::vector<int>& rc = cons(pr.out);
+    const int gci = pick(rc, "Conv"), add2 = pick(rc, "Add");
+    if (rc.size() != 2 || gci < 0 || add2 < 0) bad("the projection output must feed MHCA's grouped conv3x3 and its residual Add");
+    const ConvUnit gc = conv_unit(gci);
+    if (gc.k != 3 || gc.cout != M || gc.cin_g * gc.group != M) bad("MHCA must start with a grouped conv3x3 over the C - D channels");
+    if (gc.cin_g != 32) bad("head_dim " + std::to_string(gc.cin_g) + " (MHCA group width) is not supported, only 32");
+    relu_after(gc, "MHCA's grouped conv3x3");
+    const Node* mpn = sole(gc.out, "Conv");
+    if (!mpn) bad("MHCA's activation must feed its projection conv1x1");
+    const ConvUnit mp = conv_unit(int(mpn - nodes_.data()));
+    if (mp.k != 1 || mp.group != 1 || mp.cin_g != M || mp.cout != M || mp.relu) bad("mhca.projection must be a conv1x1 over the C - D channels");
+    for (double v : mp.shift)
+        if (v != 0.0) bad("mhca.projection has a bias; the reference's MHCA has none and the model file has no mhca.projection.bias");
+    const Node& a2 = nodes_[size_t(add2)];
+    if (!joins(a2, pr.out, mp.out) || cons(mp.out).size() != 1) bad("the MHCA output must join the projection output in one Add");
+    const Node& cn = nodes_[size_t(cat)];
+    const int64_t cax = cn.int_attr("axis", 0);
+    if (cn.in.size() != 2 || (cax != 1 && cax != -3)) bad("the Concat must join two tensors on the channel axis");
+    if (!same(cn.in[0], x1) || !same(cn.in[1], a2.out[0]) || cons(a2.out[0]).size() != 1)
+        bad("the Concat must put the E_MHSA part first and the MHCA part second (channels [0, D) and [D, C))");
+
+    // ---- Mlp ----
+    const std::string xc = cn.out[0];
+    const std::vector<int>& cc = cons(xc);
+    const int m1 = pick(cc, "Conv"), add3 = pick(cc, "Add");
+    if (cc.size() != 2 || m1 < 0 || add3 < 0) bad("the Concat must feed the Mlp's first conv1x1 and the block's residual Add");
+    const ConvUnit c1 = conv_unit(m1);
+    if (c1.k != 1 || c1.group != 1 || c1.cin_g != C) bad("mlp.conv1 must be a conv1x1 on the C channels");
+    relu_after(c1, "mlp.conv1");
+    const int H = c1.cout;
+    if (H <= 0 || H % 32 != 0) bad("the Mlp hidden width must be a multiple of 32");
+    const Node* c2n = sole(c1.out, "Conv");
+    if (!c2n) bad("the Mlp's activation must feed mlp.conv2");
+    const ConvUnit c2 = conv_unit(int(c2n - nodes_.data()));
+    if (c2.k != 1 || c2.group != 1 || c2.cin_g != H || c2.cout != C || c2.relu) bad("mlp.conv2 must be a conv1x1 from the hidden width to C channels");
+    const Node& a3 = nodes_[size_t(add3)];
+    if (!joins(a3, xc, c2.out) || cons(c2.out).size() != 1) bad("the Mlp output must join the Concat in one Add");
+
+    // ---- tensors under the names fold_ntb reads ----
+    auto identity_bn = [&](const std::string& bn, int c) {      // norm1 / norm2: already merged into the layers behind them
+        const std::vector<int64_t> d{int64_t(c)};
+        put(bn + ".weight", d, std::vector<float>(size_t(c), 1.f));
+        put(bn + ".bias", d, std::vector<float>(size_t(c), 0.f));
+        put(bn + ".running_mean", d, std::vector<float>(size_t(c), 0.f));
+        put(bn + ".running_var", d, std::vector<float>(size_t(c), kLoaderBnVar));
+    };
+    auto scaled_weight = [](const ConvUnit& u) {                // a BatchNormalization node behind a conv that has no norm of its own
+        std::vector<float> w(u.w->f);
+        const size_t per = w.size() / size_t(u.cout);
+        for (int c = 0; c < u.cout; ++c)
+            if (u.scale[size_t(c)] != 1.0)
+                for (size_t i = 0; i < per; ++i) w[size_t(c) * per + i] = float(double(w[size_t(c) * per + i]) * u.scale[size_t(c)]);
+        return w;
+    };
+    auto biased_conv = [&](const std::string& name, const ConvUnit& u) {
+        put(name + ".weight", u.w->dims, scaled_weight(u));
+        put(name + ".bias", {int64_t(u.cout)}, std::vector<float>(u.shift.begin(), u.shift.end()));
+    };
+    put_conv_bn(p + ".patch_embed.conv", p + ".patch_embed.norm", pe);
+    identity_bn(p + ".norm1", D);
+    Linear q = lin[qi];
+    if (!std_scale) {                          // softmax(s q k^T) = softmax((f q) k^T / sqrt(32)), f = s sqrt(32)
+        const double f = scale * std::sqrt(32.0);
+        for (float& w : q.w) w = float(double(w) * f);
+        for (float& b : q.b) b = float(double(b) * f);
+    }
+    put_linear(p + ".e_mhsa.q", q, true);
+    put_linear(p + ".e_mhsa.k", lin[ki], true);
+    put_linear(p + ".e_mhsa.v", lin[vi], true);
+    put_linear(p + ".e_mhsa.proj", proj, true);
+    put_conv_bn(p + ".projection.conv", p + ".projection.norm", pr);
+    put_conv_bn(p + ".mhca.group_conv3x3", p + ".mhca.norm", gc);
+    put(p + ".mhca.projection.weight", mp.w->dims, scaled_weight(mp));
+    identity_bn(p + ".norm2", C);
+    biased_conv(p + ".mlp.conv1", c1);
+    biased_conv(p + ".mlp.conv2", c2);
+    hidden = H;
+    return a3.out[0];
+}
+
 void Importer::run() {
     if (inputs_.size() != 1) fail("expected one graph input ('data'), found " + std::to_string(inputs_.size()));
     if (!outputs_.count("value_out") || !outputs_.count("policy_out"))
@@ -570,7 +847,7 @@ void Importer::run() {
     // ---- residual tower ----
     std::string cur = stem.out;
     std::vector<int> cops, kernels;
-    std::vector<std::string> se_types;
+    std::vector<std::string> se_types, transformers;
     std::string conv_block;
     int head_value = -1, head_policy = -1;
     for (int blk = 1;; ++blk) {
@@ -581,6 +858,26 @@ void Importer::run() {
             if (pick(c, "Mul") >= 0) x = se_gate(cur, p, se);
         }
         const std::vector<int> c = cons(x);
+        {   // NextViT transformer block: the block input feeds one conv1x1 (patch_embed) and no residual Add; the 'simple' variant
+            // (patch_embed the identity) feeds the token Transpose and the Add
+            const Node* n0 = c.size() == 1 ? &nodes_[size_t(c[0])] : nullptr;
+            const Tensor* w0 = n0 && n0->op == "Conv" ? init(n0->in[1]) : nullptr;
+            const bool ntb = w0 && w0->dims.size() == 4 && w0->dims[2] == 1;
+            const bool simple = c.size() == 2 && pick(c, "Transpose") >= 0 && pick(c, "Add") >= 0;
+            if (ntb || simple) {
+                if (simple) fail("transformer block " + p + ": the 'simple' NTB variant (no patch_embed / projection / MHCA / Concat) is not supported");
+                if (se != "none") fail("transformer block " + p + ": a channel gate in front of a transformer block is not supported");
+                int hidden = 0;
+                cur = transformer_block(x, p, C, hidden);
+                // channels_operating of an NTB only sizes the loader's scratch tiles (cop_max, rise_net.hip), which already holds
+                // max(3 C, hidden) for a transformer block: the Mlp width is a multiple of 32 that changes no buffer size
+                cops.push_back(hidden);
+                kernels.push_back(3);
+                se_types.push_back("none");
+                transformers.push_back("1");
+                continue;
+            }
+        }
         const int add = pick(c, "Add");
         if (add < 0) {                                     // no residual join: the heads start here
             if (se != "none") fail("a channel gate feeds no residual block at " + p);
@@ -654,7 +951,11 @@ void Importer::run() {
         if (conv_block.empty()) conv_block = kind;
         else if (conv_block != kind) fail("residual block " + p + ": mixed block families");
         se_types.push_back(se);
+        transformers.push_back("0");
     }
+    const bool any_ntb = std::find(transformers.begin(), transformers.end(), "1") != transformers.end();
+    if (any_ntb && !conv_block.empty() && conv_block != "mobile_bottlekneck_res_block")
+        fail("transformer blocks are supported in RiseV3 mobile-bottleneck towers only, not with " + conv_block);
     if (conv_block.empty()) conv_block = "mobile_bottlekneck_res_block";
 
     // ---- policy head (_PolicyHead, builder_util.py:206-243) ----
@@ -755,6 +1056,7 @@ void Importer::run() {
     m["channel_expansion"] = "0";
     m["channels_operating"] = join(cs);        // per block, as found (the loader prefers it over init/expansion)
     m["kernels"] = join(ks);
+    if (any_ntb) m["use_transformers"] = join(transformers);     // (written only for nets that have them, as export_rise does)
     m["se_types"] = join(se_types);
     m["channels_value_head"] = std::to_string(v0.cout);
     m["value_fc_size"] = std::to_string(fc);

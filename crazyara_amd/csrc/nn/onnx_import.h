@@ -3,8 +3,9 @@
 // trainer_agent_pytorch.py:588-633) loads where the reference's TensorRT backend parses it (tensorrtapi.cpp:239-295).
 //
 // The importer does not interpret arbitrary ONNX: it recognises the graphs the reference's model zoo exports --
-//   stem conv -> residual tower (mobile bottleneck blocks with optional ca_se / eca_se gates, ClassicalResidualBlock or
-//   AlphaZero ResidualBlock) -> value head (tanh or WDL + plies-to-end) and policy head (policy map or flat labels)
+//   stem conv -> residual tower (mobile bottleneck blocks with optional ca_se / eca_se gates and AlphaVile's NextViT transformer
+//   blocks, ClassicalResidualBlock or AlphaZero ResidualBlock) -> value head (tanh or WDL + plies-to-end) and policy head (policy map or
+//   flat labels)
 // -- in the flavours exporters leave them: BatchNormalization nodes or BN already folded into the convolution's weight and bias,
 // Gemm or MatMul(+Add) for Linear, shape plumbing as Reshape / Flatten with constant or computed (Shape-Gather-Concat) shapes.
 // Anything else is rejected with a message naming the node.  No protobuf library: the few messages needed are decoded from the
