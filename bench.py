@@ -1,10 +1,14 @@
 #!/usr/bin/env python
-"""Headline benchmark: NN evaluations/sec (+ MCTS nodes/sec) of the crazyhouse RISEv2-19 path at batch 256.
+"""Headline benchmark: NN evaluations/sec of the crazyhouse RISEv2-19 path at batch 256 (+ MCTS nodes/sec and the rest with --full).
 
 Contract: `python bench.py --gpus N --steps K --warmup W` (N>1 is launched by torch.distributed.run, one rank per
 GPU).  One step = one pass of the hot path over one batch of synthetic positions already resident in HBM:
 input planes -> RISEv2 19-block forward -> policy softmax + value (what NeuralNetAPI::predict computes between its
 H2D and D2H copies, engine/src/nn/tensorrtapi.cpp:195-237).  Rank 0 prints ONE JSON line.
+
+Such a plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line, nothing else.  --full adds
+everything else the benchmark measures after the timed region: the other precision modes and batch sizes, the PCIe-inclusive
+rates, the per-kernel roofline with its live PMC passes, the search / game / drop-in legs and the CPU baseline.
 
 The metric follows CrazyAra::inference (engine/src/uci/crazyara.cpp:156-181): evals/s = steps * batchSize / elapsed.
 Multi-GPU = independent replicas: no data-path collective, only the final reduction of the
@@ -497,7 +501,7 @@ def compact_record(full, detail_path):
             "traffic_unit", "traffic_source", "pmc", "per_op_ms")
     line["roofline"] = {k: rf[k] for k in keep if k in rf}
     if "whole_forward" in rf:
-        line["roofline"]["whole_forward_ms"] = rf["whole_forward"].get("ms_per_step", rf["whole_forward"]["event_ms_per_step"])
+        line["roofline"]["whole_forward_ms"] = rf["whole_forward"].get("ms_per_step", rf["whole_forward"].get("event_ms_per_step"))
         line["roofline"]["whole_forward_frac"] = rf["whole_forward"]["frac"]
     cb = full.get("cpu_baseline")
     if cb:
@@ -509,7 +513,9 @@ def compact_record(full, detail_path):
     tr = full.get("timed_region")
     if tr:
         line["timed_region"] = {k: tr[k] for k in ("repeats", "ms_per_step_min", "ms_per_step_max") if k in tr}
-    summary = {"nn_evals_per_sec": full["value"], "precision": full.get("value_precision"), "roofline_frac": rf["frac"]}
+    summary = {"nn_evals_per_sec": full["value"], "precision": full.get("value_precision")}
+    if "frac" in rf:                                                     # (the dominant kernel's roofline: --full only)
+        summary["roofline_frac"] = rf["frac"]
     for m_, r_ in full.get("modes", {}).items():
         if "evals_per_sec" in r_:                                        # (a leg that recorded a skip or an error has no rate)
             summary[f"nn_evals_per_sec_{m_}"] = r_["evals_per_sec"]
@@ -678,6 +684,11 @@ def main():
                     help="after the timed region, write what its last step computed (value, policy probabilities, auxiliary outputs: what "
                          "a caller of the path receives) as DIR/<name>.npy in float32, at most 64 MB in all; with the same arguments the "
                          "inputs are the same from run to run, so that two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run everything else the benchmark measures: the other precision modes and batch "
+                         "sizes, the PCIe-inclusive rates, the per-kernel roofline with its live PMC passes, the search / game / drop-in "
+                         "legs and the CPU baseline (the --no-* options and --timed-only leave some of them out).  Without it the line "
+                         "carries the headline and the whole forward's roofline on the timed region's clock")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-search", action="store_true")
     ap.add_argument("--simulations", type=int, default=1600)
@@ -704,9 +715,9 @@ def main():
                     help="file that receives the WHOLE result (per-mode blocks, search / game / drop-in legs, sweeps); the stdout line keeps the "
                          "contract's keys + roofline + cpu_baseline + a flat summary and stays under 6 KB")
     ap.add_argument("--timed-only", action="store_true",
-                    help="only the headline's timed region and its per-kernel events: no other modes / PCIe / search / CPU legs, no PMC child "
-                         "passes (the command scripts/gpu_round.sh runs under rocprofv3 --kernel-trace --stats, so that the trace holds "
-                         "nothing but the launches the roofline is quoted on)")
+                    help="with --full: only the headline's timed region and its per-kernel events: no other modes / PCIe / search / CPU legs, "
+                         "no PMC child passes (the command scripts/gpu_round.sh runs under rocprofv3 --kernel-trace --stats, so that the "
+                         "trace holds nothing but the launches the roofline is quoted on)")
     args = ap.parse_args()
     if args.timed_only:
         args.no_search = args.no_cpu_baseline = args.no_live_pmc = True
@@ -842,7 +853,7 @@ def main():
     mcts_configs = None
     game_configs = None
     dropin = None
-    if not args.no_search:
+    if args.full and not args.no_search:
         from crazyara_amd import openings, search, searchbench
         lanes = max(1, args.search_lanes)
         st = search.default_settings(mode=0, version_major=1, batch_size=args.search_quota)
@@ -956,69 +967,74 @@ def main():
 
     out = None
     if rank == 0:
-        # ---- roofline of the dominant kernel, timed live with hipEvents on the net's own stream ----
-        # (at least 200 replays in front of the per-launch timing, whatever --steps says: the rank has just spent tens of seconds in host-side
-        # legs, and five launches on a chip that has clocked down read 5 % long -- 0.615 ms against 0.583 for the tower with --steps 20,
-        # profiles/r06/I_bench_steps20.json; the timed region above is not touched by this)
-        settle = max(args.steps, 200)
-        ev_ms = net.time_forward(settle) / settle
-        ops = net.time_ops(10)
-        agg, cnt = {}, {}
-        for name, ms in ops:
-            agg[name] = agg.get(name, 0.0) + ms
-            cnt[name] = cnt.get(name, 0) + 1
-        dom = max(agg, key=agg.get)
         flops_total = net.flops_per_position() * args.batch
-        # algorithmic FLOPs of the dominant kernel's launches (1x1 expand/project GEMMs + depthwise of all blocks)
-        cops = cfg.channels_operating()
-        if dom in ("fused_block", "tower", "block_x3", "tower_x3", "tower_p8"):
-            dom_flops = sum(2.0 * 64 * c * (2 * cfg.channels + 9) for c in cops) * args.batch
-        elif dom == "conv_gemm_1x1":
-            dom_flops = sum(2.0 * 64 * cfg.channels * c * 2 for c in cops) * args.batch
-        elif dom == "conv_gemm_3x3":
-            dom_flops = 2.0 * 64 * 9 * (cfg.nb_input_channels * 256 + 256 * 256 + 256 * cfg.channels_policy_head) * args.batch
-        else:
-            dom_flops = flops_total
-        per_op_three = None
-        if dom == "forward":
-            # the whole forward is one launch (forward.hip); the same net as three launches gives the split per stage (informational)
-            net3 = HipAPI(local_rank, args.batch, tmp, args.precision + "-3k")
-            torch.as_tensor(net3.device_buffers()["planes"], device="cuda").copy_(x.cuda())
-            net3.time_ops(2)
-            a3 = {}
-            for name, ms in net3.time_ops(5):
-                a3[name] = a3.get(name, 0.0) + ms
-            per_op_three = {k: round(v, 4) for k, v in a3.items()}
-            net3.close()
         # float16x3: a product costs three f16 MFMAs, so the ceiling of ALGORITHMIC FLOP/s is a third of the dense f16 peak
         # float16p8: both GEMMs of the tower cost one f16 MFMA + two e5m2 products at twice the f16 rate per product = two f16 equivalents
         peak = {"float16": PEAK_F16_TFLOPS, "float16x3": PEAK_F16_TFLOPS / 3.0, "float16p8": PEAK_F16_TFLOPS / 2.0,
                 "float32": PEAK_F32_TFLOPS}[args.precision]
-        dom_ms = agg[dom]                                              # all launches of the dominant kernel in ONE step (time_ops: per-launch averages)
-        achieved = dom_flops / (dom_ms * 1e-3) / 1e12
-        traffic = None if (args.no_live_pmc or world > 1) else live_pmc_traffic(dom, args.blocks, args.batch, args.precision)
-        if traffic is None:
-            traffic = committed_pmc_traffic(dom)
-        roofline = {"bound": "mfma", "kernel": dom, "launches_per_step": cnt[dom],
-                    "avg_launch_ms": round(dom_ms / cnt[dom], 5), "achieved": round(achieved, 2), "peak": round(peak, 1),
-                    "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
-                    "frac_of_dense_f16_peak": round(achieved / PEAK_F16_TFLOPS, 4),
-                    "peak_definition": {"float16": "dense f16 MFMA peak", "float32": "exact-f32 MFMA peak",
-                                        "float16x3": "dense f16 peak / 3 (three f16 MFMAs per product)",
-                                        "float16p8": "dense f16 peak / 2 (one f16 MFMA + two e5m2 products at the 5 PFLOP/s 8-bit peak per product)"}[args.precision],
-                    **traffic,
-                    # the whole forward on the SAME clock as ms_per_step (the timed region's median); the event-timed replay beside it
-                    "whole_forward": {"ms_per_step": round(elapsed / args.steps * 1e3, 4), "event_ms_per_step": round(ev_ms, 4),
-                                      "achieved": round(flops_total / (elapsed / args.steps) / 1e12, 2),
-                                      "frac": round(flops_total / (elapsed / args.steps) / 1e12 / peak, 4)},
-                    "per_op_ms": {k: round(v, 4) for k, v in agg.items()}}
-        if per_op_three:
-            roofline["per_op_ms_as_three_launches"] = per_op_three
+        peak_definition = {"float16": "dense f16 MFMA peak", "float32": "exact-f32 MFMA peak",
+                           "float16x3": "dense f16 peak / 3 (three f16 MFMAs per product)",
+                           "float16p8": "dense f16 peak / 2 (one f16 MFMA + two e5m2 products at the 5 PFLOP/s 8-bit peak per product)"}[args.precision]
+        # the whole forward on the SAME clock as ms_per_step (the timed region); --full adds the event-timed replay beside it
+        whole_forward = {"ms_per_step": round(elapsed / args.steps * 1e3, 4),
+                         "achieved": round(flops_total / (elapsed / args.steps) / 1e12, 2),
+                         "frac": round(flops_total / (elapsed / args.steps) / 1e12 / peak, 4)}
+        roofline = {"peak": round(peak, 1), "unit": "TFLOP/s", "peak_definition": peak_definition, "whole_forward": whole_forward}
+        if args.full:
+            # ---- roofline of the dominant kernel, timed live with hipEvents on the net's own stream ----
+            # (at least 200 replays in front of the per-launch timing, whatever --steps says: the rank has just spent tens of seconds in host-side
+            # legs, and five launches on a chip that has clocked down read 5 % long -- 0.615 ms against 0.583 for the tower with --steps 20,
+            # profiles/r06/I_bench_steps20.json; the timed region above is not touched by this)
+            settle = max(args.steps, 200)
+            ev_ms = net.time_forward(settle) / settle
+            ops = net.time_ops(10)
+            agg, cnt = {}, {}
+            for name, ms in ops:
+                agg[name] = agg.get(name, 0.0) + ms
+                cnt[name] = cnt.get(name, 0) + 1
+            dom = max(agg, key=agg.get)
+            # algorithmic FLOPs of the dominant kernel's launches (1x1 expand/project GEMMs + depthwise of all blocks)
+            cops = cfg.channels_operating()
+            if dom in ("fused_block", "tower", "block_x3", "tower_x3", "tower_p8"):
+                dom_flops = sum(2.0 * 64 * c * (2 * cfg.channels + 9) for c in cops) * args.batch
+            elif dom == "conv_gemm_1x1":
+                dom_flops = sum(2.0 * 64 * cfg.channels * c * 2 for c in cops) * args.batch
+            elif dom == "conv_gemm_3x3":
+                dom_flops = 2.0 * 64 * 9 * (cfg.nb_input_channels * 256 + 256 * 256 + 256 * cfg.channels_policy_head) * args.batch
+            else:
+                dom_flops = flops_total
+            per_op_three = None
+            if dom == "forward":
+                # the whole forward is one launch (forward.hip); the same net as three launches gives the split per stage (informational)
+                net3 = HipAPI(local_rank, args.batch, tmp, args.precision + "-3k")
+                torch.as_tensor(net3.device_buffers()["planes"], device="cuda").copy_(x.cuda())
+                net3.time_ops(2)
+                a3 = {}
+                for name, ms in net3.time_ops(5):
+                    a3[name] = a3.get(name, 0.0) + ms
+                per_op_three = {k: round(v, 4) for k, v in a3.items()}
+                net3.close()
+            dom_ms = agg[dom]                                              # all launches of the dominant kernel in ONE step (time_ops: per-launch averages)
+            achieved = dom_flops / (dom_ms * 1e-3) / 1e12
+            traffic = None if (args.no_live_pmc or world > 1) else live_pmc_traffic(dom, args.blocks, args.batch, args.precision)
+            if traffic is None:
+                traffic = committed_pmc_traffic(dom)
+            whole_forward["event_ms_per_step"] = round(ev_ms, 4)
+            roofline = {"bound": "mfma", "kernel": dom, "launches_per_step": cnt[dom],
+                        "avg_launch_ms": round(dom_ms / cnt[dom], 5), "achieved": round(achieved, 2), "peak": round(peak, 1),
+                        "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
+                        "frac_of_dense_f16_peak": round(achieved / PEAK_F16_TFLOPS, 4),
+                        "peak_definition": peak_definition,
+                        **traffic,
+                        "whole_forward": whole_forward,
+                        "per_op_ms": {k: round(v, 4) for k, v in agg.items()}}
+            if per_op_three:
+                roofline["per_op_ms_as_three_launches"] = per_op_three
         # ---- the same workload in the other precision modes (N = 1 information, never `value`) ----
         #   float16   : the reference's TensorRT default (optionsuci.cpp:143-147); predict()'s outputs meet 1e-3, its logits do not
         #   float32   : exact-f32 MFMA (v_mfma_f32_16x16x4_f32), the slow mode that meets 1e-3 on the logits
         #   fp8       : e4m3 operands in the tower's GEMMs, the counterpart of the reference's INT8 mode
-        single = world == 1 and not args.timed_only
+        single = args.full and world == 1 and not args.timed_only
         modes = {}
         if single:
             for mode, mpeak, msteps in (("float16", PEAK_F16_TFLOPS, max(30, args.steps)), ("float16x3", PEAK_F16_TFLOPS / 3.0, max(20, args.steps // 2)),
@@ -1136,7 +1152,7 @@ def main():
                              "ms_per_step_max": round(max(regions) / args.steps * 1e3, 4)},
             "roofline": roofline,
         }
-        if not args.no_cpu_baseline and world == 1:                      # (rank 0 at N = 1 only: the other ranks of a node would wait for it)
+        if args.full and not args.no_cpu_baseline and world == 1:        # (rank 0 at N = 1 only: the other ranks of a node would wait for it)
             full["cpu_baseline"] = cpu_baseline(cfg, sd, x)
         if pcie is not None:
             # SURVEY 8(d) Metric 1 is CrazyAra's `inference` loop INCLUDING the host copies (crazyara.cpp:156-181): one blocking user

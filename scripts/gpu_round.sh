@@ -5,8 +5,8 @@
 #
 #   tests       pytest -m gpu (whole suite)                      smoke     __graft_entry__.smoke()
 #   newparity   the full-size parity tests of configs 2 / 3 / 5 + lane determinism
-#   bench       python bench.py (every leg) + bench_detail.json   benchquick  the NN legs only (no search / game / drop-in legs)
-#   trace       rocprofv3 --kernel-trace --stats of bench.py --timed-only, headline mode (+ float16)
+#   bench       python bench.py --full (every leg) + bench_detail.json   benchquick  the NN legs only (no search / game / drop-in legs)
+#   trace       rocprofv3 --kernel-trace --stats of bench.py --full --timed-only, headline mode (+ float16)
 #   pmc         SQ / TCC / GRBM counter passes of the headline forward (scripts/prof_forward.py), separate --pmc runs
 #   screen      scripts/coresidency_screen.py: round 4's harness net at batch 64, then the four conformant forwards at batch 256
 #   rootcause   scripts/value_head_rootcause.py (packed / scalar FC1) + scripts/ubench/neighbour_mfma.bin, every aggressor kind
@@ -36,14 +36,14 @@ run_set() {
       timeout 900 python -m pytest tests/test_nn_parity_gpu.py tests/test_lane_determinism_gpu.py -m gpu -q -k "${NEWPARITY_K:-full_size or determinism}" > $OUT/pytest_newparity.log 2>&1
       echo "pytest exit $?" >> $OUT/pytest_newparity.log; tail -6 $OUT/pytest_newparity.log ;;
     bench)
-      timeout 1200 python bench.py --detail-out $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err
+      timeout 1200 python bench.py --full --detail-out $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err
       wc -c $OUT/bench.json; cat $OUT/bench.json; tail -3 $OUT/bench.err ;;
     benchquick)
-      timeout 600 python bench.py --no-search --detail-out $OUT/benchquick_detail.json > $OUT/benchquick.json 2> $OUT/benchquick.err
+      timeout 600 python bench.py --full --no-search --detail-out $OUT/benchquick_detail.json > $OUT/benchquick.json 2> $OUT/benchquick.err
       wc -c $OUT/benchquick.json; cat $OUT/benchquick.json; tail -3 $OUT/benchquick.err ;;
     trace)
       for prec in $HEADLINE float16; do
-        (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$prec -- python $REPO/bench.py --timed-only --precision $prec --steps 300 --warmup 30 > $OUT/trace_$prec.log 2>&1)
+        (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$prec -- python $REPO/bench.py --full --timed-only --precision $prec --steps 300 --warmup 30 > $OUT/trace_$prec.log 2>&1)
         find $OUT/trace_$prec -type f ! -name "*stats*.csv" -delete
         f=$(find $OUT/trace_$prec -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/${prec}_kernel_stats.csv && head -8 $f
       done ;;

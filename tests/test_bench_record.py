@@ -106,6 +106,31 @@ def test_line_limit_holds_for_an_oversized_result_and_for_legs_without_rates():
     assert line["summary"]["nn_evals_per_sec"] == full["value"]
 
 
+PLAIN_KEYS = ("metric", "value", "value_precision", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "timed_region")
+
+
+def test_line_of_a_plain_run():
+    """Without --full the result holds the headline, its timed region and the whole forward's roofline: the line carries the contract's
+    keys and nothing of the legs that did not run."""
+    import bench
+    old = _round4_full()
+    full = {k: old[k] for k in PLAIN_KEYS}
+    full["roofline"] = {"peak": 833.3, "unit": "TFLOP/s", "peak_definition": "dense f16 peak / 3 (three f16 MFMAs per product)",
+                        "whole_forward": {"ms_per_step": 0.69, "achieved": 372.0, "frac": 0.4464}}
+    full["modes"] = {}
+    full["bench_seconds"] = 12.3
+    line = bench.compact_record(full, "d.json")
+    for k in PLAIN_KEYS[:-1]:
+        assert line[k] == full[k], k
+    assert line["timed_region"]["repeats"] == full["timed_region"]["repeats"]
+    assert line["roofline"] == {"peak": 833.3, "unit": "TFLOP/s", "peak_definition": full["roofline"]["peak_definition"],
+                                "whole_forward_ms": 0.69, "whole_forward_frac": 0.4464}
+    assert "cpu_baseline" not in line and not [k for k in line if k.startswith("value_pcie")]
+    assert line["summary"] == {"nn_evals_per_sec": full["value"], "precision": full["value_precision"], "bench_seconds": 12.3}
+    assert list(line)[-1] == "summary"
+
+
 def test_written_outputs_are_float32_and_a_seeded_sample_above_the_limit(tmp_path):
     """--dump-outputs: every array of the last timed step goes out as float32; above the limit every array keeps the same boards, the
     same ones on every call (two builds compared output for output must look at the same boards)."""
@@ -166,3 +191,22 @@ def test_dump_outputs_are_what_the_timed_steps_computed(tmp_path, hip_lib):
     value, probs = np.load(tmp_path / "a" / "value.npy"), np.load(tmp_path / "a" / "probs.npy")
     assert value.dtype == probs.dtype == np.float32 and value.shape == (16,) and probs.shape == (16, cfg.nb_policy)
     assert np.abs(value - v.numpy().reshape(-1)).max() < 1e-4 and np.abs(probs - p.numpy()).max() < 1e-4
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only(tmp_path, hip_lib):
+    """bench.py without --full: the line carries the contract's keys, and nothing but the headline ran -- no other modes, batch sizes,
+    PCIe, search, game or CPU legs, no per-kernel timing (the whole result is in the detail file)."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--blocks", "3",
+                        "--batch", "16", "--detail-out", str(tmp_path / "detail.json")], cwd=tmp_path, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["metric"] == "nn_evals_per_sec" and line["unit"] == "evals/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f16x3" and line["steps"] == 5 and line["warmup"] == 2 and line["timed_region"]["repeats"] == 1
+    assert line["value"] == pytest.approx(16 / (line["ms_per_step"] * 1e-3), rel=1e-2)
+    detail = json.load(open(tmp_path / "detail.json"))
+    assert set(detail) == set(PLAIN_KEYS) | {"roofline", "modes", "bench_seconds"}
+    assert detail["modes"] == {}
+    assert set(detail["roofline"]) == {"peak", "unit", "peak_definition", "whole_forward"}
