@@ -92,9 +92,9 @@ void launch_conv_gemm_x3(const ConvArgs& a, hipStream_t s);
 void launch_block_x3(const BlockArgs& a, hipStream_t s);          // needs dwpk, w1pk_lo, w3pk_lo; ks == 3
 void init_x3_kernel_attributes();
 int block_x3_chunk_channels();
-// a run of consecutive 3x3 bottleneck blocks in one launch (x3.hip: tower_x3_kernel): the residual stream stays in LDS as a hi / lo f16
-// pair, the SE gate of every block but the first is computed in-kernel from float weights (the first block's gate, if any, is applied
-// by the caller's SE launch)
+// a run of consecutive 3x3 bottleneck blocks in one launch (x3.hip: tower_x3_kernel): the residual stream stays in the project waves'
+// registers in f32 (its operand form in LDS as a hi / lo f16 pair), the SE gate of every block but the first is computed in-kernel from
+// float weights (the first block's gate, if any, is applied by the caller's SE launch)
 struct X3TowerBlock {
     const void *w1pk, *w1pk_lo, *w3pk, *w3pk_lo;     // as BlockArgs
     const float* dwpk;                               // [cop_pad / 16 tiles][16 rows: taps dx = -1 (dy = -1, 0, 1), dx = 0, dx = +1, BN1 bias, BN2 bias, 5 x 0][16 channels] (pack.cpp: pack_x3_depthwise_records)

@@ -919,8 +919,9 @@ void launch_heads_small(const HeadsSmallArgs& a, hipStream_t s) {
 // 3x3 + BN2 + ReLU on the f32 accumulators by DPP lane shifts (no LDS round trip, exact f32) -> split -> LDS -> project (MFMA x3)
 // into the register accumulator -> + BN3 bias + x.  8 waves, one board per workgroup.
 //   block_x3_kernel : one block per launch, x and y float [B][64][256] in HBM
-//   tower_x3_kernel : a run of consecutive 3x3 blocks in ONE launch -- the residual stream stays in LDS as its hi / lo f16 pair
-//                     (x to 2^-22) from the first block to the last, SE gates are computed in-kernel (exact f32)
+//   tower_x3_kernel : a run of consecutive 3x3 blocks in ONE launch -- the residual stream stays in the project accumulators (exact
+//                     f32, x3_stream_load) from the first block to the last, its operand form in LDS as the hi / lo f16 pair; SE gates
+//                     are computed in-kernel (exact f32)
 // ================================================================================================================
 namespace {
 struct X3Block {
@@ -1537,62 +1538,128 @@ __device__ __forceinline__ void x3_se_phase(const X3Tiles& T, const X3TowerBlock
     }
     __syncthreads();
 }
+// mean[c] (scratch, written by the caller) -> gate[c] in scratch: both FC stages, every thread of the workgroup.  Ends behind a barrier
+// with the gate valid.
+__device__ __forceinline__ void x3_se_gate_from_mean(const X3TowerBlock& d, float* scratch, int tid) {
+    constexpr int GRP = 36;
+    f32x4 wa[16], wb[16];
+    auto load_thread_weights = [&](const float* base, f32x4 (&dst)[16]) {
+        const f32x4* pk = reinterpret_cast<const f32x4*>(base) + tid;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) dst[i] = pk[i * 512];
+    };
+    load_thread_weights(d.se_w1t, wa);
+    load_thread_weights(d.se_kind == 1 ? d.se_w2t : d.se_w1t + size_t(16) * 512 * 4, wb);
+    __syncthreads();                                                    // the means are in
+    x3_se_fcs(d, scratch, scratch + 8 * GRP, scratch + 12 * GRP, wa, wb, tid);
+}
+
+// The residual stream of the float16x3 towers lives in the project accumulators of the waves that own its couts, exact f32: a wave's
+// NJ cout tiles from tile0 on (tower_x3_kernel: 2, tower_x3_roles_kernel's PROJECT waves: 4), x[j][t][r] = x[square of tile row
+// t * 16 + l15][channel (tile0 + j) * 16 + lg * 4 + r].  A block adds its BN3 bias and then its project sums ON it; the block epilogue only
+// writes the operand tiles xh / xl of the new x.  Both tower kernels run these helpers: the same bits.
+template <int NJ>
+__device__ __forceinline__ void x3_stream_load(f32x4 (&x)[NJ][4], const float* xb, int tile0, int l15, int lg) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) x[j][t] = *reinterpret_cast<const f32x4*>(xb + size_t(x3_square(t * 16 + l15)) * X3Block::C + (tile0 + j) * 16 + lg * 4);
+}
+template <int NJ>
+__device__ __forceinline__ void x3_stream_store(const f32x4 (&x)[NJ][4], float* yb, int tile0, int l15, int lg) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) *reinterpret_cast<f32x4*>(yb + size_t(x3_square(t * 16 + l15)) * X3Block::C + (tile0 + j) * 16 + lg * 4) = x[j][t];
+}
+template <int NJ>
+__device__ __forceinline__ void x3_stream_add_bias(f32x4 (&x)[NJ][4], const float* b3, int tile0, int lg) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const f32x4 bs = *reinterpret_cast<const f32x4*>(b3 + (tile0 + j) * 16 + lg * 4);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) x[j][t] += bs;
+    }
+}
+template <int NJ>
+__device__ __forceinline__ void x3_stream_write_tiles(const X3Tiles& T, const f32x4 (&x)[NJ][4], int tile0, int l15, int lg) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int co0 = (tile0 + j) * 16 + lg * 4;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int rr = t * 16 + l15;
+            const float v[4] = {x[j][t][0], x[j][t][1], x[j][t][2], x[j][t][3]};
+            half4 h, l;
+            split4(v, h, l);
+            *reinterpret_cast<half4*>(T.xh + rr * X3Block::XROW + co0) = h;
+            *reinterpret_cast<half4*>(T.xl + rr * X3Block::XROW + co0) = l;
+        }
+    }
+}
+// SE gate of a block on the stream in the registers (the waves that hold the stream; every other wave runs x3_se_gate_from_mean and a
+// barrier beside it): squeeze from the registers -- the four square tiles, then the 16 lanes of the row -- the gate, x := x * gate (the
+// residual uses the gated x, builder_util.py:473-475), the operand tiles rewritten.  scratch: the t2 tiles, idle between blocks.  Ends
+// behind a barrier.
+template <int NJ>
+__device__ __forceinline__ void x3_stream_se(const X3Tiles& T, const X3TowerBlock& d, f32x4 (&x)[NJ][4], float* scratch, int tile0, int tid) {
+    constexpr int GRP = 36;
+    const int lane = tid & 63, l15 = lane & 15, lg = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        float sum[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sum[r] = (x[j][0][r] + x[j][1][r]) + (x[j][2][r] + x[j][3][r]);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            sum[r] += dpp_mov<0x111>(sum[r]);    // row_shr:1
+            sum[r] += dpp_mov<0x112>(sum[r]);    // row_shr:2
+            sum[r] += dpp_mov<0x114>(sum[r]);    // row_shr:4
+            sum[r] += dpp_mov<0x118>(sum[r]);    // row_shr:8 -> lane 15 of the row holds the row's sum
+        }
+        if (l15 == 15) {
+            const int c = (tile0 + j) * 16 + lg * 4;                     // channel c at (c / 32) * 36 + c % 32
+#pragma unroll
+            for (int r = 0; r < 4; ++r) scratch[((c + r) >> 5) * GRP + ((c + r) & 31)] = sum[r] * (1.f / 64.f);
+        }
+    }
+    x3_se_gate_from_mean(d, scratch, tid);
+    const float* se_gate = scratch + 12 * GRP;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const f32x4 g = *reinterpret_cast<const f32x4*>(se_gate + (tile0 + j) * 16 + lg * 4);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) x[j][t] *= g;
+    }
+    x3_stream_write_tiles<NJ>(T, x, tile0, l15, lg);
+    __syncthreads();
+}
 }  // namespace
 
 __global__ __launch_bounds__(512) void tower_x3_kernel(const X3TowerArgs a) {
     using G = X3Block;
-    constexpr int C = G::C, XROW = G::XROW, NJ = G::NJ;
+    constexpr int C = G::C, NJ = G::NJ;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const X3Tiles T = x3_tiles(smem);
     const int b = blockIdx.x;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l15 = lane & 15, lg = lane >> 4;
     x3_stage_tile(T, a.x + size_t(b) * 64 * C, nullptr, tid);
+    f32x4 accX[NJ][4];                                          // the residual stream of this wave's 32 couts (x3_stream_load)
+    x3_stream_load<NJ>(accX, a.x + size_t(b) * 64 * C, wave * NJ, l15, lg);
     __syncthreads();
     for (int blk = 0; blk < a.nblocks; ++blk) {
         const X3TowerBlock& d = a.blocks[blk];
-        if (blk > 0 && d.se_kind != 0) x3_se_phase(T, d, reinterpret_cast<float*>(T.t2h), tid);
+        if (blk > 0 && d.se_kind != 0) x3_stream_se<NJ>(T, d, accX, reinterpret_cast<float*>(T.t2h), wave * NJ, tid);
         const X3Weights W = x3_weights(d.w1pk, d.w1pk_lo, d.w3pk, d.w3pk_lo, d.dwpk, d.cop_pad);
-        f32x4 accP[NJ][4];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {                          // the project accumulators start at the BN3 bias of their 4 couts
-            const f32x4 bs = *reinterpret_cast<const f32x4*>(d.b3 + (wave * NJ + j) * 16 + lg * 4);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) accP[j][t] = bs;
-        }
-        x3_chunks(T, W, accP);
-        // block epilogue: new stream = x + body(x), split again, in place.  A wave rewrites exactly the columns (its 32 couts) it reads
-        // here, and the chunk loop's closing barrier is behind every other read of the tiles.
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int co0 = (wave * NJ + j) * 16 + lg * 4;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int sq = t * 16 + l15;
-                float rh[4], rl[4], v[4];
-                load4<half_t>(T.xh + sq * XROW + co0, rh);
-                load4<half_t>(T.xl + sq * XROW + co0, rl);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = accP[j][t][r] + (rh[r] + rl[r]);
-                half4 h, l;
-                split4(v, h, l);
-                *reinterpret_cast<half4*>(T.xh + sq * XROW + co0) = h;
-                *reinterpret_cast<half4*>(T.xl + sq * XROW + co0) = l;
-            }
-        }
+        x3_stream_add_bias<NJ>(accX, d.b3, wave * NJ, lg);
+        x3_chunks(T, W, accX);
+        // block epilogue: accX IS the new stream; its operand forms go to LDS for the next block unless that block gates it first
+        // (x3_stream_se writes them then) or there is none (the result leaves from the registers).  A wave rewrites exactly its own
+        // columns, and the chunk loop's closing barrier is behind every other read of the tiles.
+        if (blk + 1 < a.nblocks && a.blocks[blk + 1].se_kind == 0) x3_stream_write_tiles<NJ>(T, accX, wave * NJ, l15, lg);
         __syncthreads();
     }
-    // stream -> HBM as float, 32-byte pieces per thread
-    float* yb = a.y + size_t(b) * 64 * C;
-#pragma unroll 1
-    for (int i = tid; i < 64 * (C / 8); i += G::NTHR) {
-        const int sq = i / (C / 8), v = i - sq * (C / 8), r = x3_row(sq);
-        float fh[8], fl[8];
-        load8<half_t>(T.xh + r * XROW + v * 8, fh);
-        load8<half_t>(T.xl + r * XROW + v * 8, fl);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) fh[j] += fl[j];
-        store8<float>(yb + size_t(sq) * C + v * 8, fh);
-    }
+    x3_stream_store<NJ>(accX, a.y + size_t(b) * 64 * C, wave * NJ, l15, lg);
 }
 
 // ---- small batches: one block per launch, G workgroups per board (kernels.h: X3SplitArgs) ----
@@ -1842,7 +1909,8 @@ __global__ __launch_bounds__(512) void tower_x3_roles_kernel(const X3TowerArgs a
     for (int blk = 0; blk < a.nblocks; ++blk) {
         const X3TowerBlock& d = a.blocks[blk];
         if (blk > 0 && d.se_kind != 0) {
-            x3_se_phase(T, d, reinterpret_cast<float*>(T.t2h), tid);
+            x3_se_gate_from_mean(d, reinterpret_cast<float*>(T.t2h), tid);     // (the squeeze and x *= gate are the PROJECT waves': x3_stream_se)
+            __syncthreads();                                            // the gated operand tiles are written
             // (never requested in front of a gate phase.  The flag alone does not tell the register allocator: an empty definition of every
             // fragment here ends their live ranges in front of the phase, which needs the registers)
             first_chunk_requested = false;
@@ -2034,9 +2102,13 @@ __global__ __launch_bounds__(512) void tower_x3_roles_kernel(const X3TowerArgs a
         }
     }
     } else {
+    // PROJECT waves: the residual stream of this wave's 64 couts lives in accX (x3_stream_load) from the first block to the last
+    constexpr int NJ = 4;
+    f32x4 accX[NJ][4];
+    x3_stream_load<NJ>(accX, a.x + size_t(b) * 64 * C, w * NJ, l15, lg);
     for (int blk = 0; blk < a.nblocks; ++blk) {
         const X3TowerBlock& d = a.blocks[blk];
-        if (blk > 0 && d.se_kind != 0) x3_se_phase(T, d, reinterpret_cast<float*>(T.t2h), tid);
+        if (blk > 0 && d.se_kind != 0) x3_stream_se<NJ>(T, d, accX, reinterpret_cast<float*>(T.t2h), w * NJ, tid);
         const X3Weights W = x3_weights(d.w1pk, d.w1pk_lo, d.w3pk, d.w3pk_lo, d.dwpk, d.cop_pad);
         const int n = W.cop_pad / CK;
         const int nslab3 = W.cop_pad >> 5;
@@ -2047,9 +2119,9 @@ __global__ __launch_bounds__(512) void tower_x3_roles_kernel(const X3TowerArgs a
         {
             // project weight window: 2 of a chunk's 4 k-slabs x 4 cout tiles x (hi, lo), running on across chunk boundaries
 #if defined(CRA_DEVELOPMENT) && defined(CRA_X3_PW)
-            constexpr int PW = CRA_X3_PW, NJ = 4;
+            constexpr int PW = CRA_X3_PW;
 #else
-            constexpr int PW = 2, NJ = 4;
+            constexpr int PW = 2;
 #endif
             half8 p_h[PW][NJ], p_l[PW][NJ];
             auto load_p = [&](int k, int s2) {                         // cout tile = w * 4 + j, K slab = k * 4 + s2
@@ -2067,13 +2139,7 @@ __global__ __launch_bounds__(512) void tower_x3_roles_kernel(const X3TowerArgs a
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) p_h[s2][j] = p_l[s2][j] = *reinterpret_cast<const half8*>(T.xl + lane * 8);
             }
-            f32x4 accP[NJ][4];                                          // couts (w * 4 + j) * 16 + lg * 4 .. + 3, squares t * 16 + l15
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {                              // the accumulators start at the BN3 bias of their 4 couts
-                const f32x4 bs = *reinterpret_cast<const f32x4*>(d.b3 + (w * NJ + j) * 16 + lg * 4);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) accP[j][t] = bs;
-            }
+            x3_stream_add_bias<NJ>(accX, d.b3, w * NJ, lg);             // the block's project sums are accumulated on x + b3
 #pragma unroll
             for (int s2 = 0; s2 < PW; ++s2) load_p(0, s2);
             if constexpr (!(X3_ABL & 32)) {
@@ -2105,15 +2171,15 @@ __global__ __launch_bounds__(512) void tower_x3_roles_kernel(const X3TowerArgs a
 #pragma unroll
                     for (int j = 0; j < NJ; ++j)
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) x3_mfma(p_l[s2 % PW][j], bh[s2 & 1][t], accP[j][t], !(X3_ABL & 4));
+                        for (int t = 0; t < 4; ++t) x3_mfma(p_l[s2 % PW][j], bh[s2 & 1][t], accX[j][t], !(X3_ABL & 4));
 #pragma unroll
                     for (int j = 0; j < NJ; ++j)
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) x3_mfma(p_h[s2 % PW][j], bl[s2 & 1][t], accP[j][t], !(X3_ABL & 4));
+                        for (int t = 0; t < 4; ++t) x3_mfma(p_h[s2 % PW][j], bl[s2 & 1][t], accX[j][t], !(X3_ABL & 4));
 #pragma unroll
                     for (int j = 0; j < NJ; ++j)
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) x3_mfma(p_h[s2 % PW][j], bh[s2 & 1][t], accP[j][t], !(X3_ABL & 4));
+                        for (int t = 0; t < 4; ++t) x3_mfma(p_h[s2 % PW][j], bh[s2 & 1][t], accX[j][t], !(X3_ABL & 4));
                     if (s2 + PW < CK / 32) load_p(kk, s2 + PW);
                     else load_p(kk + 1 < n ? kk + 1 : kk, s2 + PW - CK / 32);
                     if (s2 == 1) X3_STAMP(9);
@@ -2125,42 +2191,16 @@ __global__ __launch_bounds__(512) void tower_x3_roles_kernel(const X3TowerArgs a
                 }
                 X3_STAMP(11);
             }
-            // block epilogue: new stream = x + body(x), split again, in place (every EXPAND wave is behind its last read of the tiles: it
-            // waits at the barrier below)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const int co0 = (w * NJ + j) * 16 + lg * 4;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const int sq = t * 16 + l15;
-                    float rh[4], rl[4], v[4];
-                    load4<half_t>(T.xh + sq * XROW + co0, rh);
-                    load4<half_t>(T.xl + sq * XROW + co0, rl);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = accP[j][t][r] + (rh[r] + rl[r]);
-                    half4 h, l;
-                    split4(v, h, l);
-                    *reinterpret_cast<half4*>(T.xh + sq * XROW + co0) = h;
-                    *reinterpret_cast<half4*>(T.xl + sq * XROW + co0) = l;
-                }
-            }
+            // block epilogue: accX IS the new stream; its operand forms go to LDS for the next block unless that block gates it first
+            // (x3_stream_se writes them then) or there is none (the result leaves from the registers).  Every EXPAND wave is behind its
+            // last read of the tiles: it waits at the barrier below.
+            if (blk + 1 < a.nblocks && a.blocks[blk + 1].se_kind == 0) x3_stream_write_tiles<NJ>(T, accX, w * NJ, l15, lg);
             { const int kk = n; X3_STAMP(12); }
             __syncthreads();
             { const int kk = n; X3_STAMP(13); }
         }
     }
-    }
-    // stream -> HBM as float, 32-byte pieces per thread
-    float* yb = a.y + size_t(b) * 64 * C;
-#pragma unroll 1
-    for (int i = tid; i < 64 * (C / 8); i += G::NTHR) {
-        const int sq = i / (C / 8), v = i - sq * (C / 8), r = x3_row(sq);
-        float fh[8], fl[8];
-        load8<half_t>(T.xh + r * XROW + v * 8, fh);
-        load8<half_t>(T.xl + r * XROW + v * 8, fl);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) fh[j] += fl[j];
-        store8<float>(yb + size_t(sq) * C + v * 8, fh);
+    x3_stream_store<NJ>(accX, a.y + size_t(b) * 64 * C, w * NJ, l15, lg);     // the stream -> HBM straight from the registers
     }
 }
 
@@ -2174,79 +2214,9 @@ __global__ __launch_bounds__(512) void tower_x3_roles_kernel(const X3TowerArgs a
 //    permute; the e4m3 form of the first build paid for its conversions what the matrix pipe gained, sets j and k).
 //  * The tiles in LDS hold the operand forms only: the stream tile xh = rne_f16(x) + a byte row [hi8, 256 B | lo8, 256 B] where float16x3 keeps
 //    the lo half; the depthwise output t2h + a byte row [hi8, 128 B | lo8, 128 B] (272-byte pitch) where float16x3 keeps t2l.
-//  * The residual stream itself lives in the PROJECT waves' accumulators: wave v holds x of its 64 couts x 64 squares in f32 (exact, where
-//    float16x3 rebuilds x = hi + lo from LDS to 2^-22), the project sums of a block are accumulated ON it -- in the project weights' scale:
-//    x := (x + b3) * 2^p in front of the block, x := x * 2^-p behind it, both exact -- and the block epilogue only writes the operand forms of
-//    the new x.  SE gates: squeeze from the registers, gate as before, x *= gate in the registers.
+//  * The residual stream lives in the PROJECT waves' accumulators as in float16x3 (x3_stream_load), the project sums of a block accumulated
+//    on it in the project weights' scale: x := (x + b3) * 2^p in front of the block, x := x * 2^-p behind it, both exact.
 // The roles are separated at the top level (the PROJECT waves' 64 registers of x must not be live in the EXPAND waves' code).
-namespace {
-// mean[c] (LDS scratch, written by the PROJECT waves) -> gate[c] in LDS: the middle of x3_se_phase, every thread of the workgroup.
-// Ends behind a barrier with se_gate valid.
-__device__ __forceinline__ void x3_se_gate_from_mean(const X3TowerBlock& d, float* scratch, int tid) {
-    constexpr int GRP = 36;
-    float* se_mean = scratch;              // [8][36]
-    float* se_h = scratch + 8 * GRP;       // [4][36]
-    float* se_gate = se_h + 4 * GRP;       // [256]
-    f32x4 wa[16], wb[16];
-    auto load_thread_weights = [&](const float* base, f32x4 (&dst)[16]) {
-        const f32x4* pk = reinterpret_cast<const f32x4*>(base) + tid;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) dst[i] = pk[i * 512];
-    };
-    load_thread_weights(d.se_w1t, wa);
-    load_thread_weights(d.se_kind == 1 ? d.se_w2t : d.se_w1t + size_t(16) * 512 * 4, wb);
-    __syncthreads();                                                    // the means are in
-    auto dot32 = [](const f32x4 (&w)[16], const float* v, float& s0, float& s1) {
-#pragma unroll
-        for (int k4 = 0; k4 < 8; ++k4) {
-            const f32x4 m = *reinterpret_cast<const f32x4*>(v + 4 * k4);
-            s0 = fmaf(w[2 * k4][0], m[0], s0); s1 = fmaf(w[2 * k4][1], m[0], s1);
-            s0 = fmaf(w[2 * k4][2], m[1], s0); s1 = fmaf(w[2 * k4][3], m[1], s1);
-            s0 = fmaf(w[2 * k4 + 1][0], m[2], s0); s1 = fmaf(w[2 * k4 + 1][1], m[2], s1);
-            s0 = fmaf(w[2 * k4 + 1][2], m[3], s0); s1 = fmaf(w[2 * k4 + 1][3], m[3], s1);
-        }
-    };
-    if (d.se_kind == 1) {
-        {
-            const int j2 = tid >> 3, kq = tid & 7;
-            float s0 = 0.f, s1 = 0.f;
-            dot32(wa, se_mean + kq * GRP, s0, s1);
-            s0 += dpp_mov<0x111>(s0); s1 += dpp_mov<0x111>(s1);
-            s0 += dpp_mov<0x112>(s0); s1 += dpp_mov<0x112>(s1);
-            s0 += dpp_mov<0x114>(s0); s1 += dpp_mov<0x114>(s1);
-            if (kq == 7) {
-                float* h = se_h + (j2 >> 4) * GRP + 2 * (j2 & 15);
-                h[0] = fmaxf(s0, 0.f);
-                h[1] = fmaxf(s1, 0.f);
-            }
-        }
-        __syncthreads();
-        {
-            const int c2 = tid >> 2, kq = tid & 3;
-            float s0 = 0.f, s1 = 0.f;
-            dot32(wb, se_h + kq * GRP, s0, s1);
-            s0 += dpp_mov<0x111>(s0); s1 += dpp_mov<0x111>(s1);
-            s0 += dpp_mov<0x112>(s0); s1 += dpp_mov<0x112>(s1);
-            if (kq == 3) {
-                se_gate[2 * c2] = hard_sigmoid(s0);
-                se_gate[2 * c2 + 1] = hard_sigmoid(s1);
-            }
-        }
-    } else {
-        const int c2 = tid >> 2, kq = tid & 3;
-        float s0 = 0.f, s1 = 0.f;
-        dot32(wa, se_mean + (2 * kq) * GRP, s0, s1);
-        dot32(wb, se_mean + (2 * kq + 1) * GRP, s0, s1);
-        s0 += dpp_mov<0x111>(s0); s1 += dpp_mov<0x111>(s1);
-        s0 += dpp_mov<0x112>(s0); s1 += dpp_mov<0x112>(s1);
-        if (kq == 3) {
-            se_gate[2 * c2] = hard_sigmoid(d.se_b[2 * c2] + s0);
-            se_gate[2 * c2 + 1] = hard_sigmoid(d.se_b[2 * c2 + 1] + s1);
-        }
-    }
-    __syncthreads();
-}
-}  // namespace
 
 // byte position of channel c inside a byte row of the residual stream: the 16-byte pieces of a 64-channel step in the order A0 B0 A1 B1
 __device__ __forceinline__ int x8_pos(int c) { return (c & ~0x30) | ((c & 0x10) << 1) | ((c & 0x20) >> 1); }
