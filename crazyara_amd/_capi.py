@@ -43,6 +43,14 @@ SIGNATURES = {
     "mi_net_submit_boards": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi_net_submit_boards_gathered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]),
+    # game-phase experts
+    "mi_net_create_experts": (C.c_void_p, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int]),
+    "mi_net_num_experts": (C.c_int, [C.c_void_p]),
+    "mi_expert_dirs": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int]),
+    "mi_net_set_expert_routing": (C.c_int, [C.c_void_p, C.c_int]),
+    "mi_net_submit_boards_phases": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_int_p]),
+    "mi_net_predict_routed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_desc_game_phase": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     # environment
     "mi_pos_create": (C.c_void_p, [C.c_char_p, C.c_int, C.c_char_p]),
     "mi_pos_clone": (C.c_void_p, [C.c_void_p]),

@@ -54,6 +54,38 @@ mi_net* mi_net_create(const char* model_dir, int device_id, int batch_size, cons
 }
 void mi_net_destroy(mi_net* net) { delete net; }
 
+mi_net* mi_net_create_experts(const char* model_dir, int device_id, int batch_size, const char* precision, int game_phase_definition) {
+    mi_net* h = nullptr;
+    if (guard([&] { h = new mi_net(model_dir, device_id, batch_size, precision, game_phase_definition); })) return nullptr;
+    return h;
+}
+int mi_net_num_experts(const mi_net* net) { return net ? net->net.num_experts() : 0; }
+int mi_net_set_expert_routing(mi_net* net, int routing) {
+    if (!net) { g_err = "null net"; return 1; }
+    return guard([&] { net->net.set_expert_routing(routing); });
+}
+int mi_net_submit_boards_phases(mi_net* net, const void* descs_host, int n_valid, int* phases_out) {
+    if (!net || (n_valid > 0 && (!descs_host || !phases_out))) { g_err = "null argument to mi_net_submit_boards_phases"; return 1; }
+    return guard([&] { net->net.route_phases(descs_host, n_valid, phases_out); });
+}
+int mi_net_predict_routed(mi_net* net, const float* in_planes, const int* phases, float* value, float* probs, float* aux) {
+    if (!net || !in_planes || !phases || !value || !probs) { g_err = "null argument to mi_net_predict_routed"; return 1; }
+    return guard([&] { net->net.predict_routed(in_planes, phases, value, probs, aux); });
+}
+int mi_expert_dirs(const char* model_dir, int batch_size, int game_phase_definition, char* out, int cap) {
+    if (!model_dir) { g_err = "null argument to mi_expert_dirs"; return -1; }
+    int n = -1;
+    if (guard([&] {
+            const std::vector<cra::ExpertDir> dirs = cra::discover_experts(model_dir, batch_size, game_phase_definition);
+            std::string text;
+            for (const cra::ExpertDir& d : dirs) text += d.dir + "\n";
+            if (out && cap > 0) snprintf(out, size_t(cap), "%s", text.c_str());
+            n = int(dirs.size());
+        }))
+        return -1;
+    return n;
+}
+
 int mi_net_calibrate_int8(const char* model_dir, int device_id, const float* planes, int n_boards) {
     if (!model_dir) { g_err = "null argument to mi_net_calibrate_int8"; return 1; }
     return guard([&] { (void)cra::calibrate_int8(model_dir, device_id, planes, n_boards); });

@@ -88,6 +88,10 @@ int mi_pos_game_phase(const mi_pos* pos, int num_phases, int definition) {
     cra_guard([&] { phase = pos->pos.game_phase(unsigned(num_phases), definition); });
     return phase;
 }
+int mi_desc_game_phase(const void* desc192, int num_phases, int definition) {
+    if (!desc192 || num_phases < 1 || (definition != 0 && definition != 1)) return -1;
+    return cra::desc_game_phase(*static_cast<const cra::BoardDesc*>(desc192), num_phases, definition);
+}
 int mi_pos_insufficient_material(const mi_pos* pos) { return pos && pos->pos.draw_by_insufficient_material() ? 1 : 0; }
 int mi_pos_plies_from_null(const mi_pos* pos) { return pos ? pos->pos.plies_from_null() : 0; }
 int mi_pos_in_check(const mi_pos* pos) { return pos && pos->pos.checkers() != 0 ? 1 : 0; }

@@ -300,4 +300,54 @@ CRA_HD float plane_value(const BoardDesc& d, int layout, bool normalize, int ch,
     return 0.0f;
 }
 
+// Game phase of a descriptor: Board::get_phase (board.cpp:540-587) restated over BoardDesc, equal to chess::Position::game_phase on the
+// position the descriptor was packed from.  definition 0 = lichess (three phases whatever num_phases says: majors and minors, back-rank
+// sparseness, mixedness of the Divider), 1 = movecount.  Everything get_phase reads is in the descriptor but the game ply itself:
+// total_move_cout() = gamePly / 2 (board.cpp:127-130) is fullmove - 1 here (pack_desc: fullmove = game_ply / 2 + 1).
+enum GamePhaseDefinition : int { PHASE_LICHESS = 0, PHASE_MOVECOUNT = 1 };
+
+CRA_HD int desc_game_phase(const BoardDesc& d, int num_phases, int definition) {
+    using namespace planes_detail;
+    if (definition == PHASE_LICHESS) {
+        const int mm = popc(d.bb[1] | d.bb[2] | d.bb[3] | d.bb[4] | d.bb[7] | d.bb[8] | d.bb[9] | d.bb[10]);
+        if (mm <= 6) return 2;
+        if (mm <= 10) return 1;
+        const uint64_t white = color_bb(d, 0), black = color_bb(d, 1);
+        if (popc(white & 0xffull) <= 3 || popc(black & (0xffull << 56)) <= 3) return 1;
+        int mix = 0;                                            // get_mixedness: every 2x2 window, scored by (white, black) count and rank
+        for (int r = 0; r < 7; ++r)
+            for (int f = 0; f < 7; ++f) {
+                const uint64_t window = 0x303ull << (r * 8 + f);
+                const int w = popc(white & window), b = popc(black & window), y = r + 1;
+                int s = 0;
+                switch (w * 5 + b) {
+                    case 1 * 5 + 0: s = 1 + (8 - y); break;
+                    case 2 * 5 + 0: s = 2 + (y > 2 ? y - 2 : 0); break;
+                    case 3 * 5 + 0:
+                    case 4 * 5 + 0: s = 3 + (y > 1 ? y - 1 : 0); break;
+                    case 0 * 5 + 1: s = 1 + y; break;
+                    case 1 * 5 + 1: s = 5 + (y > 3 ? y - 3 : 3 - y); break;
+                    case 2 * 5 + 1: s = 4 + y; break;
+                    case 3 * 5 + 1: s = 5 + y; break;
+                    case 0 * 5 + 2: s = 2 + (y < 6 ? 6 - y : 0); break;
+                    case 1 * 5 + 2: s = 4 + (6 - y); break;
+                    case 2 * 5 + 2: s = 7; break;
+                    case 0 * 5 + 3:
+                    case 0 * 5 + 4: s = 3 + (y < 7 ? 7 - y : 0); break;
+                    case 1 * 5 + 3: s = 5 + (6 - y); break;
+                    default: break;
+                }
+                mix += s;
+            }
+        return mix > 150 ? 1 : 0;
+    }
+    if (definition == PHASE_MOVECOUNT) {
+        if (num_phases <= 1) return 0;
+        const double phase_length = double(long(42.85 / double(num_phases) + 0.5));       // std::round of a positive number
+        const double g = double(d.fullmove > 0 ? d.fullmove - 1 : 0) / phase_length;
+        return g > double(num_phases - 1) ? num_phases - 1 : int(g);
+    }
+    return 0;
+}
+
 }  // namespace cra

@@ -18,5 +18,7 @@ void board_to_planes(const Position& pos, int layout, bool normalize, float* out
 
 // GPU builder: n descriptors (device memory) -> float NCHW planes [n][C][64]
 void launch_planes_from_desc(const BoardDesc* d_desc, int n, int layout, int normalize, float* d_planes, void* stream);
+// the same for a routed batch: slot w of d_planes is built from descriptor board_of[w] (n entries, each an index into desc)
+void launch_planes_from_desc_indexed(const BoardDesc* desc, const int* board_of, int n, int layout, int normalize, float* d_planes, void* stream);
 
 }  // namespace cra

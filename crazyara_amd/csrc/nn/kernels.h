@@ -375,6 +375,17 @@ template <typename T> void launch_value_final(const ValueFinalArgs& a, hipStream
 void launch_gather_probs(const float* probs, int nb_policy, const uint16_t* idx, const uint32_t* cnt, int stride, int n_slots, float* out,
                          const float* value_dev, float* value_out, int batch, const float* aux_dev, float* aux_out, hipStream_t s);
 
+// The same for a group of a routed batch (an expert set, rise_net.hip): the expert ran its boards packed, slot w = board board_of[w] of
+// the batch.  Slot w's priors go to row board_of[w] of `out`, read through that board's idx / cnt; its value and aux to that board's places.
+void launch_gather_probs_indexed(const float* probs, int nb_policy, const uint16_t* idx, const uint32_t* cnt, int stride, const int* board_of,
+                                 int n_slots, float* out, const float* value_dev, float* value_out, const float* aux_dev, float* aux_out,
+                                 hipStream_t s);
+// whole probability rows (and logits rows, when given) of a group into the batch's tensors, value and aux with them
+void launch_scatter_rows_indexed(const float* probs, const float* logits, int nb_policy, const int* board_of, int n_slots, float* probs_out,
+                                 float* logits_out, const float* value_dev, float* value_out, const float* aux_dev, float* aux_out, hipStream_t s);
+// float planes [row = C * 64] of a group out of the batch's: dst slot w = src board board_of[w]
+void launch_gather_planes_indexed(const float* src, const int* board_of, int n_slots, int row, float* dst, hipStream_t s);
+
 // Attention core of a NextViT transformer block (attention.hip): per board and head of 32 channels, softmax(Q K^T * 32^-0.5) V over the
 // 64 squares.  qkv: [B][64][3D] T (q = channels 0 .. D-1, k = D .. 2D-1, v = 2D .. 3D-1; head h = channels 32 h .. 32 h + 31 of each),
 // out: [B][64][D] T.  mode 0: float16 (T = half_t), 1: float32 (T = float, exact f32 MFMA), 2: float16x3 (T = float, hi / lo split operands).

@@ -526,6 +526,65 @@ void launch_gather_probs(const float* probs, int nb_policy, const uint16_t* idx,
                        value_out, batch, aux_dev, aux_out);
 }
 
+// ---- routed batches (an expert set, rise_net.hip): an expert ran its group packed (slot w = board board_of[w] of the batch) ----
+// gather_probs_kernel for a group: slot w's priors, value and aux go to board board_of[w]'s places in the caller's buffers, read through
+// that board's index list
+__global__ void gather_probs_indexed_kernel(const float* __restrict__ probs, int nb_policy, const uint16_t* __restrict__ idx,
+                                            const uint32_t* __restrict__ cnt, int stride, const int* __restrict__ board_of,
+                                            float* __restrict__ out, const float* __restrict__ value_dev, float* __restrict__ value_out,
+                                            const float* __restrict__ aux_dev, float* __restrict__ aux_out) {
+    const int w = blockIdx.x;
+    const int board = board_of[w];
+    if (threadIdx.x == 0) value_out[board] = value_dev[w];
+    if (aux_dev != nullptr && threadIdx.x < 4) aux_out[board * 4 + threadIdx.x] = aux_dev[w * 4 + threadIdx.x];
+    const uint32_t n = min(cnt[board], uint32_t(stride));
+    const float* row = probs + size_t(w) * nb_policy;
+    const size_t base = size_t(board) * stride;
+    for (uint32_t j = threadIdx.x; j < n; j += blockDim.x) out[base + j] = row[idx[base + j]];
+}
+void launch_gather_probs_indexed(const float* probs, int nb_policy, const uint16_t* idx, const uint32_t* cnt, int stride, const int* board_of,
+                                 int n_slots, float* out, const float* value_dev, float* value_out, const float* aux_dev, float* aux_out,
+                                 hipStream_t s) {
+    hipLaunchKernelGGL(gather_probs_indexed_kernel, dim3(n_slots), dim3(64), 0, s, probs, nb_policy, idx, cnt, stride, board_of, out, value_dev,
+                       value_out, aux_dev, aux_out);
+}
+
+// whole rows of a group into the batch's tensors: dst row board_of[w] = src row w (probabilities, optionally logits; value and aux ride along)
+__global__ __launch_bounds__(256) void scatter_rows_indexed_kernel(const float* __restrict__ probs, const float* __restrict__ logits, int nb_policy,
+                                                                   const int* __restrict__ board_of, float* __restrict__ probs_out,
+                                                                   float* __restrict__ logits_out, const float* __restrict__ value_dev,
+                                                                   float* __restrict__ value_out, const float* __restrict__ aux_dev,
+                                                                   float* __restrict__ aux_out) {
+    const int w = blockIdx.x;
+    const int board = board_of[w];
+    if (threadIdx.x == 0) value_out[board] = value_dev[w];
+    if (aux_dev != nullptr && threadIdx.x < 4) aux_out[board * 4 + threadIdx.x] = aux_dev[w * 4 + threadIdx.x];
+    const float* src = probs + size_t(w) * nb_policy;
+    float* dst = probs_out + size_t(board) * nb_policy;
+    for (int i = threadIdx.x; i < nb_policy; i += 256) dst[i] = src[i];
+    if (logits != nullptr) {
+        src = logits + size_t(w) * nb_policy;
+        dst = logits_out + size_t(board) * nb_policy;
+        for (int i = threadIdx.x; i < nb_policy; i += 256) dst[i] = src[i];
+    }
+}
+void launch_scatter_rows_indexed(const float* probs, const float* logits, int nb_policy, const int* board_of, int n_slots, float* probs_out,
+                                 float* logits_out, const float* value_dev, float* value_out, const float* aux_dev, float* aux_out, hipStream_t s) {
+    hipLaunchKernelGGL(scatter_rows_indexed_kernel, dim3(n_slots), dim3(256), 0, s, probs, logits, nb_policy, board_of, probs_out, logits_out,
+                       value_dev, value_out, aux_dev, aux_out);
+}
+
+// float planes of a group out of the batch's planes: dst slot w = src board board_of[w] (row = C * 64 floats)
+__global__ __launch_bounds__(256) void gather_planes_indexed_kernel(const float* __restrict__ src, const int* __restrict__ board_of, int row,
+                                                                    float* __restrict__ dst) {
+    const float* in = src + size_t(board_of[blockIdx.x]) * row;
+    float* out = dst + size_t(blockIdx.x) * row;
+    for (int i = threadIdx.x; i < row; i += 256) out[i] = in[i];
+}
+void launch_gather_planes_indexed(const float* src, const int* board_of, int n_slots, int row, float* dst, hipStream_t s) {
+    hipLaunchKernelGGL(gather_planes_indexed_kernel, dim3(n_slots), dim3(256), 0, s, src, board_of, row, dst);
+}
+
 void launch_softmax(const float* logits, float* probs, int batch, int n, hipStream_t s) {
     hipLaunchKernelGGL(softmax_kernel, dim3(batch), dim3(256), 0, s, logits, probs, n);
 }

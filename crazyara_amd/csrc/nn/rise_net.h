@@ -47,8 +47,34 @@ struct Precision {
 };
 Precision parse_precision(const std::string& precision);   // throws std::invalid_argument
 
+// One expert of a model directory of game-phase experts: the subdirectory and the phase its name ends in
+struct ExpertDir {
+    int phase = 0;
+    std::string dir;          // with a trailing '/'
+};
+// Discovery of a phase-expert model directory, host only (fill_nn_vectors, uci/crazyara.cpp:566-600: the subdirectories whose name ends in
+// a digit, "phaseNone" and the like skipped; the digit is the phase, neuralnetapi.cpp:229-239) with NeuralNetAPIUser's two asserts
+// (neuralnetapiuser.cpp:34-47: phase < number of experts, no phase twice) as refusals, and the agreement of the experts' designs (input
+// channels, policy size, aux count, version) read from their model files.  Returns the experts ordered by phase; throws
+// std::invalid_argument naming the directory.  definition: 0 lichess (exactly three experts), 1 movecount.
+std::vector<ExpertDir> discover_experts(const std::string& model_dir, int batch_size, int game_phase_definition);
+
 class RiseNet {
 public:
+    // An expert set behind one handle: one net per game phase (discover_experts), every board of a call evaluated by the net of ITS phase
+    // (desc_game_phase, chess/planes.h).  Precision float16x3 only.  submit_boards / submit_boards_gathered / wait work as on a plain net;
+    // predict / submit (planes carry no phase) are refused, predict_routed takes the phases from the caller.
+    struct ExpertSet {};
+    RiseNet(ExpertSet, const std::string& model_dir, int device_id, int batch_size, const std::string& precision, int game_phase_definition);
+    int num_experts() const { return int(experts_.size()); }
+    enum Routing : int { ROUTE_PER_BOARD = 0, ROUTE_MAJORITY = 1 };      // majority: the reference's rule (SearchThread::select_nn_index)
+    void set_expert_routing(int routing);
+    int expert_routing() const { return routing_; }
+    // routing only: the phase (= expert) every valid board of the call would go to under the set's routing
+    void route_phases(const void* descs_host, int n_valid, int* phases_out, int routing = -1) const;
+    // the whole fixed batch from float planes, board b on expert phases[b]; blocking, host pointers as predict()
+    void predict_routed(const float* in_planes, const int* phases, float* value, float* probs, float* aux);
+
     // model_path: a .cranet file, or a directory searched like get_onnx_model_name() (neuralnetapi.cpp:57-73).
     // precision: "float16" (f16 MFMA operands, f32 accumulate; the reference TensorRT default, optionsuci.cpp:143-147)
     //            or "fp8" ("float8"; "int8" is accepted as the reference's name for its reduced-precision mode): float16 with e4m3
@@ -78,12 +104,13 @@ public:
     void submit(const float* in_planes, float* value, float* probs, float* aux);
     void wait();
     // descriptor-fed variant: 192-byte BoardDesc per position, planes expanded on the GPU (csrc/chess/planes_kernel.hip)
-    void submit_boards(const void* descs_host, int n_valid, int layout, float* value, float* probs, float* aux);
+    // routing (both descriptor-fed calls): an expert set's routing for THIS call, -1 = the set's own (set_expert_routing); plain nets ignore it
+    void submit_boards(const void* descs_host, int n_valid, int layout, float* value, float* probs, float* aux, int routing = -1);
     // the same, but only the probabilities the search will read come back: idx[s * stride .. + cnt[s]) are the policy indices of slot s's
     // legal moves, gathered[] (same layout) receives probs[s][idx].  Every host buffer (descs, idx, cnt, value, gathered, aux) must come
     // from mi_host_alloc / hipHostMalloc: the kernels read and write them in place, there is no copy.
     void submit_boards_gathered(const void* descs_host, int n_valid, int layout, const uint16_t* idx, const uint32_t* cnt, uint32_t stride,
-                                float* value, float* gathered, float* aux);
+                                float* value, float* gathered, float* aux, int routing = -1);
 
     // INT8 calibration (the reference: Int8EntropyCalibrator2 over ChessBatchStream, tensorrtapi.cpp:334-360): on a net made with Precision
     // "float16-unfused" -- every tensor of a block passes through HBM there -- runs the n boards (float planes, NCHW, as predict() takes
@@ -197,6 +224,22 @@ private:
     bool small_path_ok() const;
     RiseNet& small_net();
     struct Turn;                       // forwards of different streams take turns when one fills the chip (rise_net.hip)
+    // ---- an expert set (rise_net.hip: "routed batches") ----
+    std::vector<std::unique_ptr<RiseNet>> experts_;    // by phase; empty on a plain net.  The set itself has no ops of its own
+    int phase_definition_ = 0, routing_ = ROUTE_PER_BOARD;
+    // (ONE buffer per set, rewritten at the start of every call: a call must have been waited for before the next one is submitted --
+    // the discipline the caller's own pinned buffers ask for anyway)
+    int* route_ = nullptr;             // pinned: board_of[batch] (grouped by expert, ascending board index inside a group), then offsets[experts + 1]
+    hipEvent_t fork_ev_ = nullptr;
+    std::vector<hipEvent_t> join_ev_;
+    struct Group;                      // what one expert is handed of a routed call
+    void group_boards(const int* phases, int n_valid);
+    void routed_call(int n_valid, const Group& proto);
+    void run_group(const Group& g);    // on an expert: planes of its boards, forward of g.n boards, results to the boards' own slots
+    void refuse_on_expert_set(const char* what, const char* why = nullptr) const;
+    void submit_boards_routed(const void* descs_host, int n_valid, int layout, float* value, float* probs, float* aux, int routing);
+    void submit_boards_gathered_routed(const void* descs_host, int n_valid, int layout, const uint16_t* idx, const uint32_t* cnt, uint32_t stride,
+                                       float* value, float* gathered, float* aux, int routing);
     int cu_count_ = 256;
     int device_ = 0;
     int launches_ = 0;

@@ -10,6 +10,10 @@
 #include <fstream>
 #include <type_traits>
 #include <stdexcept>
+#include <algorithm>
+#include <cctype>
+#include <dirent.h>
+#include <sys/stat.h>
 
 #include "kernels.h"
 #include "onnx_import.h"
@@ -283,6 +287,10 @@ RiseNet::~RiseNet() {
         (void)hipStreamSynchronize(stream_);
         if (owns_stream_ && stream_slot_ < 0) turns_forget_stream(device_, stream_);
     }
+    experts_.clear();                            // (an expert set: every routed call was joined into stream_, drained above)
+    if (route_) (void)hipHostFree(route_);
+    if (fork_ev_) (void)hipEventDestroy(fork_ev_);
+    for (hipEvent_t e : join_ev_) (void)hipEventDestroy(e);
     if (graph_exec_) (void)hipGraphExecDestroy(graph_exec_);
     if (graph_) (void)hipGraphDestroy(graph_);
     impl_.reset();
@@ -1331,6 +1339,7 @@ const char* RiseNet::op_name(int i) const {
 }
 
 void RiseNet::time_ops(int iters, float* ms) {
+    refuse_on_expert_set("per-op timing");
     HIP_CHECK(hipSetDevice(device_));
     hipEvent_t e0, e1;
     HIP_CHECK(hipEventCreate(&e0));
@@ -1388,6 +1397,7 @@ void screen_compare(const char* a, const char* b, size_t bytes, unsigned* bad, h
 }  // namespace
 
 int RiseNet::dev_screen_prepare() {
+    refuse_on_expert_set("the co-residency screen");
     HIP_CHECK(hipSetDevice(device_));
     Impl& im = *impl_;
     if (!im.screen.empty()) return int(im.screen.size());
@@ -1435,6 +1445,7 @@ int RiseNet::dev_screen_prepare() {
 }
 
 long RiseNet::dev_screen_run(int op, int launches, long* words) {
+    refuse_on_expert_set("the co-residency screen");
     HIP_CHECK(hipSetDevice(device_));
     Impl& im = *impl_;
     if (im.screen.empty()) throw std::runtime_error("dev_screen_run: dev_screen_prepare first");
@@ -1459,6 +1470,7 @@ long RiseNet::dev_screen_run(int op, int launches, long* words) {
 }
 
 std::string RiseNet::dev_screen_info(int op) const {
+    refuse_on_expert_set("the co-residency screen");
     const Impl& im = *impl_;
     if (op < 0 || op >= int(im.screen.size())) return "";
     size_t bytes = 0;
@@ -1468,6 +1480,7 @@ std::string RiseNet::dev_screen_info(int op) const {
 }
 
 void RiseNet::dev_launch_op(int op, int iters) {
+    refuse_on_expert_set("a single op");
     HIP_CHECK(hipSetDevice(device_));
     if (op < 0 || op >= int(impl_->ops.size())) throw std::invalid_argument("op index out of range");
     for (int it = 0; it < iters; ++it) {
@@ -1477,6 +1490,7 @@ void RiseNet::dev_launch_op(int op, int iters) {
 }
 
 float RiseNet::time_forward(int iters) {
+    refuse_on_expert_set("a device-resident forward");
     HIP_CHECK(hipSetDevice(device_));
     hipEvent_t e0, e1;
     HIP_CHECK(hipEventCreate(&e0));
@@ -1495,6 +1509,10 @@ float RiseNet::time_forward(int iters) {
 void RiseNet::keep_logits(bool on) {
     if (on == keep_logits_) return;
     keep_logits_ = on;
+    for (auto& e : experts_) {                // an expert set: its experts (and their companions) keep them, the set collects the rows
+        e->keep_logits(on);
+        if (e->small_) e->small_->keep_logits(on);
+    }
     if (launches_ > 1 && graph_exec_) {      // forwards of several launches replay a captured graph: capture again with the new head arguments
         HIP_CHECK(hipStreamSynchronize(stream_));
         (void)hipGraphExecDestroy(graph_exec_);
@@ -1531,6 +1549,7 @@ void RiseNet::capture() {
 }
 
 void RiseNet::forward_on(hipStream_t s) {
+    refuse_on_expert_set("a forward without boards");
     if (prec_.fp16()) enqueue<half_t>(s); else enqueue<float>(s);
 }
 
@@ -1614,6 +1633,7 @@ struct RiseNet::Turn {
 // graph launch's own cost between consecutive replays: it goes into the stream as a plain launch.  Everything else replays the graph.
 // CRA_DEVICE_GRAPH=1 forces the graph (A/B timing).
 void RiseNet::forward_async() {
+    refuse_on_expert_set("a device-resident forward");
     touch_stream();
     Turn turn(*this);
     if (launches_ == 1 && !dev_.device_graph) {
@@ -1657,6 +1677,7 @@ bool RiseNet::buffers_are_pinned(const float* in_planes, float* value, float* pr
 }
 
 void RiseNet::submit(const float* in_planes, float* value, float* probs, float* aux) {
+    refuse_on_expert_set("predict / submit", "float planes carry no game phase -- mi_net_predict_routed takes the phases from the caller, mi_net_submit_boards derives them from the descriptors");
     HIP_CHECK(hipSetDevice(device_));   // every predict selects its device, tensorrtapi.cpp:198
     const size_t B = design_.batch;
     // Zero-copy or staged?  With pinned buffers the kernels can read the planes and write value / probabilities across PCIe themselves: no
@@ -1699,13 +1720,17 @@ bool RiseNet::small_path_ok() const {
 }
 RiseNet& RiseNet::small_net() { return *small_; }
 
-void RiseNet::submit_boards(const void* descs_host, int n_valid, int layout, float* value, float* probs, float* aux) {
+void RiseNet::submit_boards(const void* descs_host, int n_valid, int layout, float* value, float* probs, float* aux, int routing) {
     HIP_CHECK(hipSetDevice(device_));
     const size_t B = design_.batch;
     if (n_valid < 0 || size_t(n_valid) > B) throw std::invalid_argument("n_valid out of range");
     if (layout_channels(layout) != design_.nb_input_channels)
         throw std::invalid_argument("plane layout has " + std::to_string(layout_channels(layout)) + " channels, net expects " +
                                     std::to_string(design_.nb_input_channels));
+    if (!experts_.empty()) {
+        submit_boards_routed(descs_host, n_valid, layout, value, probs, aux, routing);
+        return;
+    }
     if (n_valid > 0 && n_valid <= kBoardSplitMaxBatch && small_path_ok()) {
         small_net().submit_boards(descs_host, n_valid, layout, value, probs, aux);      // (into this net's stream: wait() as ever)
         return;
@@ -1726,7 +1751,7 @@ void RiseNet::submit_boards(const void* descs_host, int n_valid, int layout, flo
 }
 
 void RiseNet::submit_boards_gathered(const void* descs_host, int n_valid, int layout, const uint16_t* idx, const uint32_t* cnt, uint32_t stride,
-                                     float* value, float* gathered, float* aux) {
+                                     float* value, float* gathered, float* aux, int routing) {
     HIP_CHECK(hipSetDevice(device_));
     const size_t B = design_.batch;
     if (n_valid < 0 || size_t(n_valid) > B) throw std::invalid_argument("n_valid out of range");
@@ -1734,6 +1759,10 @@ void RiseNet::submit_boards_gathered(const void* descs_host, int n_valid, int la
     if (layout_channels(layout) != design_.nb_input_channels)
         throw std::invalid_argument("plane layout has " + std::to_string(layout_channels(layout)) + " channels, net expects " +
                                     std::to_string(design_.nb_input_channels));
+    if (!experts_.empty()) {
+        submit_boards_gathered_routed(descs_host, n_valid, layout, idx, cnt, stride, value, gathered, aux, routing);
+        return;
+    }
     if (n_valid > 0 && n_valid <= kBoardSplitMaxBatch && small_path_ok()) {          // few boards on a net made for many: the companion net
         small_net().submit_boards_gathered(descs_host, n_valid, layout, idx, cnt, stride, value, gathered, aux);
         return;
@@ -1791,6 +1820,297 @@ void RiseNet::submit_boards_gathered(const void* descs_host, int n_valid, int la
                         (d_aux_ && aux) ? d_aux_ : nullptr, aux, stream_);
 }
 
+// ---- routed batches: an expert set (one net per game phase behind one handle) ----
+// Every board of a call is evaluated by the net of ITS game phase.  The forward is one workgroup per board and boards never meet inside
+// it, so 256 boards split over three experts are still 256 workgroups -- three launches of n_e workgroups each instead of one of 256.
+// Per call the HOST derives the phases from the descriptors (desc_game_phase), groups the board indices by expert (stable) and writes the
+// list into a pinned buffer of the set: it needs the counts to size the launches, so grouping on the device would only add a
+// synchronisation.  Expert e then runs, in ITS stream (the library's per-queue streams: the groups share the chip instead of queueing),
+//   planes_from_desc_indexed (slot w <- descriptor board_of[w])  ->  its own forward over n_e boards  ->  gather_probs_indexed
+// (slot w's priors / value / aux -> board board_of[w]'s places in the caller's pinned buffers).  A group of at most 64 boards goes where a
+// plain net sends it (the companion net's split-board forward), a larger one runs the full-size net's launches on n_e workgroups
+// (dyn_n_).  The tower, block, conv and head kernels are the plain net's: a board's numbers depend on its expert's weights and on
+// nothing else.  Fork and join are events; the host waits for nothing between the groups, and a routed call is ONE turn (Turn).
+namespace {
+struct HostDesign { int cin = 0, policy = 0, aux = 0, version = 0; };
+HostDesign host_design(const std::string& dir, int batch_size) {
+    const std::string file = find_model_file(dir, batch_size);
+    NetFile nf;
+    if (file.size() > 5 && file.compare(file.size() - 5, 5, ".onnx") == 0) import_onnx(dir + file, nf);
+    else nf.load(dir + file);
+    HostDesign d;
+    d.cin = int(nf.num("nb_input_channels"));
+    d.policy = nf.num("select_policy_from_plane", 1) != 0 ? int(nf.num("channels_policy_head")) * kSquares : int(nf.num("n_labels", 0));
+    d.aux = (nf.num("use_wdl") != 0 && nf.num("use_plys_to_end") != 0) ? 4 : 0;
+    d.version = read_version_from_string(file);
+    return d;
+}
+}  // namespace
+
+std::vector<ExpertDir> discover_experts(const std::string& model_dir, int batch_size, int definition) {
+    if (model_dir.empty()) throw std::invalid_argument("The given directory must not be empty.");
+    if (definition != PHASE_LICHESS && definition != PHASE_MOVECOUNT)
+        throw std::invalid_argument("game phase definition " + std::to_string(definition) + ": 0 lichess, 1 movecount");
+    const std::string root = model_dir.back() == '/' ? model_dir : model_dir + "/";
+    std::vector<std::string> names;
+    if (DIR* d = opendir(root.c_str())) {
+        while (dirent* e = readdir(d)) names.emplace_back(e->d_name);
+        closedir(d);
+    } else {
+        throw std::invalid_argument("The given directory at " + root + " cannot be opened");
+    }
+    std::sort(names.begin(), names.end());
+    auto has_ext = [](const std::string& f, const char* ext) { const size_t n = strlen(ext); return f.size() > n && f.compare(f.size() - n, n, ext) == 0; };
+    std::vector<ExpertDir> found;
+    for (const std::string& n : names) {
+        if (n == "." || n == "..") continue;
+        struct stat st;
+        if (stat((root + n).c_str(), &st) != 0) continue;
+        if (!S_ISDIR(st.st_mode)) {
+            if (has_ext(n, ".cranet") || has_ext(n, ".onnx"))
+                throw std::invalid_argument("The given directory at " + root + " holds the model file " + n + " itself: that is a single net, not a set of game-phase experts -- use mi_net_create");
+            continue;
+        }
+        if (!std::isdigit(static_cast<unsigned char>(n.back()))) continue;           // "phaseNone" and the like
+        ExpertDir e;
+        e.dir = root + n + "/";
+        e.phase = read_game_phase_from_string(e.dir);
+        found.push_back(e);
+    }
+    if (found.empty()) throw std::invalid_argument("The given directory at " + root + " holds no game-phase subdirectory (a name that ends in the phase digit, e.g. phase0)");
+    const int n = int(found.size());
+    std::vector<const ExpertDir*> by_phase(size_t(n), nullptr);
+    for (const ExpertDir& e : found) {
+        if (e.phase < n && by_phase[size_t(e.phase)])
+            throw std::invalid_argument("The given directory at " + root + " holds game phase " + std::to_string(e.phase) + " twice: " + by_phase[size_t(e.phase)]->dir + " and " + e.dir);
+        if (e.phase < n) by_phase[size_t(e.phase)] = &e;
+    }
+    for (const ExpertDir& e : found)
+        if (e.phase >= n) {
+            int missing = 0;
+            while (missing < n && by_phase[size_t(missing)]) ++missing;
+            throw std::invalid_argument("The given directory at " + root + " holds " + std::to_string(n) + " expert(s) but " + e.dir + " is for game phase " + std::to_string(e.phase) +
+                                        ": the phases must be 0 .. " + std::to_string(n - 1) + ", phase " + std::to_string(missing) + " is missing");
+        }
+    if (definition == PHASE_LICHESS && n != 3)
+        throw std::invalid_argument("The given directory at " + root + " holds " + std::to_string(n) + " expert(s): the lichess game-phase definition has three phases (board.cpp:544)");
+    std::vector<ExpertDir> out;
+    for (const ExpertDir* e : by_phase) out.push_back(*e);
+    const HostDesign d0 = host_design(out[0].dir, batch_size);
+    for (size_t i = 1; i < out.size(); ++i) {
+        const HostDesign d = host_design(out[i].dir, batch_size);
+        auto differ = [&](const char* what, int a, int b) {
+            if (a != b)
+                throw std::invalid_argument("The experts of " + root + " disagree in " + what + ": " + out[0].dir + " has " + std::to_string(a) + ", " + out[i].dir + " has " + std::to_string(b));
+        };
+        differ("input channels", d0.cin, d.cin);
+        differ("policy size", d0.policy, d.policy);
+        differ("aux outputs", d0.aux, d.aux);
+        differ("version", d0.version, d.version);
+    }
+    return out;
+}
+
+struct RiseNet::Group {
+    const int* board_of = nullptr;     // the group's boards (indices into the batch), device-visible
+    int n = 0;
+    int layout = 0;
+    const void* descs = nullptr;       // the batch's descriptors (device-visible), or
+    const float* planes = nullptr;     // the batch's float planes on the device (predict_routed)
+    const uint16_t* idx = nullptr;     // gathered form: the batch's index lists and where the priors go
+    const uint32_t* cnt = nullptr;
+    uint32_t stride = 0;
+    float* gathered = nullptr;
+    float* probs = nullptr;            // whole-vector form: the batch's tensors
+    float* logits = nullptr;
+    float* value = nullptr;            // [batch], [batch][4] or null
+    float* aux = nullptr;
+};
+
+RiseNet::RiseNet(ExpertSet, const std::string& model_dir, int device_id, int batch_size, const std::string& precision, int game_phase_definition)
+    : device_(device_id), impl_(new Impl) {
+    if (batch_size <= 0) throw std::invalid_argument("batch size must be positive");
+    precision_arg_ = precision;
+    prec_ = parse_precision(precision);
+    // (every kernel-family suffix too: "-1wg", "-3k", "-8w", "-1b" / "-2b", "-unfused", "-perblock" are A/B variants no routed call was checked in)
+    if (prec_.mode != Precision::Mode::Float16x3 || !prec_.fused || !prec_.tower || !prec_.one_launch || prec_.thin_waves || !prec_.board_split || prec_.boards_per_wg != 0)
+        throw std::invalid_argument("an expert set runs Precision float16x3 (got '" + precision + "'): the routed forward is checked bit for bit in that mode only");
+    const std::vector<ExpertDir> dirs = discover_experts(model_dir, batch_size, game_phase_definition);      // host only: refusals come before the device is touched
+    phase_definition_ = game_phase_definition;
+    int ndev = 0;
+    HIP_CHECK(hipGetDeviceCount(&ndev));
+    if (device_id < 0 || device_id >= ndev) throw std::invalid_argument("device id out of range");
+    HIP_CHECK(hipSetDevice(device_id));
+    for (const ExpertDir& d : dirs) experts_.emplace_back(new RiseNet(d.dir, device_id, batch_size, precision));
+    design_ = experts_[0]->design_;
+    design_.game_phase = 0;
+    cu_count_ = experts_[0]->cu_count_;
+    model_name_ = experts_[0]->model_name_;
+    model_file_path_ = model_dir;
+    if (dev_.own_stream || device_id >= 64) HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    else stream_slot_ = take_net_stream(device_id, &stream_);
+    const size_t B = size_t(batch_size);
+    d_desc_ = impl_->dalloc(B * sizeof(BoardDesc));
+    d_planes_ = static_cast<float*>(impl_->dalloc(B * design_.nb_input_channels * kSquares * sizeof(float)));
+    d_value_ = static_cast<float*>(impl_->dalloc(B * sizeof(float)));
+    d_probs_ = static_cast<float*>(impl_->dalloc(B * design_.nb_policy * sizeof(float)));
+    d_logits_ = static_cast<float*>(impl_->dalloc(B * design_.nb_policy * sizeof(float)));
+    if (design_.nb_aux) d_aux_ = static_cast<float*>(impl_->dalloc(B * 4 * sizeof(float)));
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&route_), (B + experts_.size() + 1) * sizeof(int), hipHostMallocDefault));
+    HIP_CHECK(hipEventCreateWithFlags(&fork_ev_, hipEventDisableTiming));
+    join_ev_.assign(experts_.size(), nullptr);
+    for (hipEvent_t& e : join_ev_) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+}
+
+void RiseNet::refuse_on_expert_set(const char* what, const char* why) const {
+    if (!experts_.empty())
+        throw std::invalid_argument(std::string(what) + " on an expert set: " +
+                                    (why ? why : "the set has no launches of its own, its experts run the forward -- make the expert's directory a plain net (mi_net_create) for this"));
+}
+
+void RiseNet::set_expert_routing(int routing) {
+    if (experts_.empty()) throw std::invalid_argument("expert routing: this net is no expert set");
+    if (routing != ROUTE_PER_BOARD && routing != ROUTE_MAJORITY) throw std::invalid_argument("expert routing: 0 per board, 1 majority");
+    routing_ = routing;
+}
+
+void RiseNet::route_phases(const void* descs_host, int n_valid, int* phases_out, int routing) const {
+    if (experts_.empty()) throw std::invalid_argument("this net is no expert set");
+    if (n_valid < 0 || n_valid > design_.batch) throw std::invalid_argument("n_valid out of range");
+    if (routing < 0) routing = routing_;               // (the set's own, mi_net_set_expert_routing; a search lane names its settings' per call)
+    if (routing != ROUTE_PER_BOARD && routing != ROUTE_MAJORITY) throw std::invalid_argument("expert routing: 0 per board, 1 majority");
+    const BoardDesc* d = static_cast<const BoardDesc*>(descs_host);
+    const int E = num_experts();
+    int count[10] = {};
+    for (int b = 0; b < n_valid; ++b) {
+        const int p = std::min(desc_game_phase(d[b], E, phase_definition_), E - 1);
+        phases_out[b] = p;
+        ++count[p];
+    }
+    if (routing == ROUTE_MAJORITY && n_valid > 0) {
+        // SearchThread::select_nn_index (searchthread.cpp:386-401): std::max_element over the std::map of the phases that occur -- the
+        // first of the largest counts, i.e. the lowest phase among ties
+        int best = -1;
+        for (int p = 0; p < E; ++p)
+            if (count[p] > 0 && (best < 0 || count[p] > count[best])) best = p;
+        for (int b = 0; b < n_valid; ++b) phases_out[b] = best;
+    }
+}
+
+// route_ <- the boards 0 .. n - 1 grouped by expert (ascending board index inside a group), then the experts' offsets
+void RiseNet::group_boards(const int* phases, int n) {
+    const int E = num_experts();
+    int* off = route_ + design_.batch;
+    for (int e = 0; e <= E; ++e) off[e] = 0;
+    for (int b = 0; b < n; ++b) {
+        if (phases[b] < 0 || phases[b] >= E) throw std::invalid_argument("board " + std::to_string(b) + " has game phase " + std::to_string(phases[b]) + ", the set has " + std::to_string(E) + " experts");
+        ++off[phases[b] + 1];
+    }
+    for (int e = 0; e < E; ++e) off[e + 1] += off[e];
+    int fill[10];
+    for (int e = 0; e < E; ++e) fill[e] = off[e];
+    for (int b = 0; b < n; ++b) route_[fill[phases[b]]++] = b;
+}
+
+void RiseNet::run_group(const Group& g) {
+    if (g.n <= kBoardSplitMaxBatch && small_path_ok()) {           // few boards on a net made for many: the companion net, as a plain call
+        small_net().run_group(g);
+        return;
+    }
+    if (g.descs) launch_planes_from_desc_indexed(static_cast<const BoardDesc*>(g.descs), g.board_of, g.n, g.layout, 1, d_planes_, stream_);
+    else launch_gather_planes_indexed(g.planes, g.board_of, g.n, design_.nb_input_channels * kSquares, d_planes_, stream_);
+    // a forward of g.n boards: the companion net's launches take the boards of the call already, the full-size net's the same way
+    // (launch_op: every board-batched launch is one workgroup -- or a fixed number of them -- per board)
+    dyn_n_ = (g.n < design_.batch && !dev_.no_small_path) ? g.n : 0;
+    touch_stream();
+    forward_on(stream_);               // (no Turn: the groups of one routed call run side by side, the SET takes the turn)
+    dyn_n_ = 0;
+    float* aux_dev = (d_aux_ && g.aux) ? d_aux_ : nullptr;
+    if (g.gathered)
+        launch_gather_probs_indexed(d_probs_, design_.nb_policy, g.idx, g.cnt, int(g.stride), g.board_of, g.n, g.gathered, d_value_, g.value, aux_dev, g.aux, stream_);
+    else
+        launch_scatter_rows_indexed(d_probs_, g.logits ? d_logits_ : nullptr, design_.nb_policy, g.board_of, g.n, g.probs, g.logits, d_value_, g.value, aux_dev, g.aux, stream_);
+    HIP_CHECK(hipGetLastError());
+}
+
+void RiseNet::routed_call(int n_valid, const Group& proto) {
+    (void)n_valid;
+    const int* off = route_ + design_.batch;
+    touch_stream();
+    Turn turn(*this);                  // one routed call is one turn: whatever fills the chip before it is in front of ALL its groups
+    HIP_CHECK(hipEventRecord(fork_ev_, stream_));
+    for (int e = 0; e < num_experts(); ++e) {
+        const int n_e = off[e + 1] - off[e];
+        if (n_e == 0) continue;
+        RiseNet& x = *experts_[size_t(e)];
+        HIP_CHECK(hipStreamWaitEvent(x.stream_, fork_ev_, 0));
+        Group g = proto;
+        g.board_of = route_ + off[e];
+        g.n = n_e;
+        x.run_group(g);
+        HIP_CHECK(hipEventRecord(join_ev_[size_t(e)], x.stream_));
+        HIP_CHECK(hipStreamWaitEvent(stream_, join_ev_[size_t(e)], 0));
+    }
+}
+
+void RiseNet::submit_boards_routed(const void* descs_host, int n_valid, int layout, float* value, float* probs, float* aux, int routing) {
+    if (n_valid == 0) return;
+    std::vector<int> phases(static_cast<size_t>(n_valid));
+    route_phases(descs_host, n_valid, phases.data(), routing);
+    group_boards(phases.data(), n_valid);
+    HIP_CHECK(hipMemcpyAsync(d_desc_, descs_host, size_t(n_valid) * sizeof(BoardDesc), hipMemcpyHostToDevice, stream_));
+    Group g;
+    g.layout = layout;
+    g.descs = d_desc_;
+    g.probs = d_probs_;
+    g.logits = keep_logits_ ? d_logits_ : nullptr;
+    g.value = d_value_;
+    g.aux = d_aux_;
+    routed_call(n_valid, g);
+    const size_t rows = size_t(n_valid);
+    HIP_CHECK(hipMemcpyAsync(value, d_value_, rows * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipMemcpyAsync(probs, d_probs_, rows * design_.nb_policy * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    if (d_aux_ && aux) HIP_CHECK(hipMemcpyAsync(aux, d_aux_, rows * 4 * sizeof(float), hipMemcpyDeviceToHost, stream_));
+}
+
+void RiseNet::submit_boards_gathered_routed(const void* descs_host, int n_valid, int layout, const uint16_t* idx, const uint32_t* cnt, uint32_t stride,
+                                            float* value, float* gathered, float* aux, int routing) {
+    if (n_valid == 0) return;
+    std::vector<int> phases(static_cast<size_t>(n_valid));
+    route_phases(descs_host, n_valid, phases.data(), routing);
+    group_boards(phases.data(), n_valid);
+    // no copy commands, as on a plain net: descriptors, index lists and results stay in the caller's pinned buffers
+    Group g;
+    g.layout = layout;
+    g.descs = descs_host;
+    g.idx = idx;
+    g.cnt = cnt;
+    g.stride = stride;
+    g.gathered = gathered;
+    g.value = value;
+    g.aux = (d_aux_ && aux) ? aux : nullptr;
+    routed_call(n_valid, g);
+}
+
+void RiseNet::predict_routed(const float* in_planes, const int* phases, float* value, float* probs, float* aux) {
+    if (experts_.empty()) throw std::invalid_argument("mi_net_predict_routed: this net is no expert set");
+    HIP_CHECK(hipSetDevice(device_));
+    const size_t B = design_.batch;
+    group_boards(phases, int(B));
+    HIP_CHECK(hipMemcpyAsync(d_planes_, in_planes, B * design_.nb_input_channels * kSquares * sizeof(float), hipMemcpyHostToDevice, stream_));
+    Group g;
+    g.planes = d_planes_;
+    g.probs = d_probs_;
+    g.logits = keep_logits_ ? d_logits_ : nullptr;
+    g.value = d_value_;
+    g.aux = d_aux_;
+    routed_call(int(B), g);
+    HIP_CHECK(hipMemcpyAsync(value, d_value_, B * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipMemcpyAsync(probs, d_probs_, B * design_.nb_policy * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    if (d_aux_ && aux) HIP_CHECK(hipMemcpyAsync(aux, d_aux_, B * 4 * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    wait();
+}
+
 void RiseNet::wait() {
     struct Done {                                                       // the predict is over however this call ends
         RiseNet& n;
@@ -1821,6 +2141,7 @@ void RiseNet::predict(const float* in_planes, float* value, float* probs, float*
 }
 
 void* RiseNet::enable_block_dump(int* n_tiles) {
+    refuse_on_expert_set("the block dump");
     HIP_CHECK(hipSetDevice(device_));
     Op* tower = nullptr;
     for (Op& op : impl_->ops)
@@ -1865,6 +2186,7 @@ std::vector<std::pair<float, float>> read_int8_calibration(const std::string& mo
 }
 
 std::vector<std::pair<float, float>> RiseNet::calibration_maxima(const float* planes_host, int n_boards) {
+    refuse_on_expert_set("calibration", "an expert set runs Precision float16x3 only");
     if (prec_.fused || !prec_.fp16() || prec_.fp8_tower()) throw std::logic_error("calibration_maxima: a net made with Precision float16-unfused");
     if (!planes_host || n_boards <= 0) throw std::invalid_argument("calibration needs at least one board");
     HIP_CHECK(hipSetDevice(device_));

@@ -30,7 +30,7 @@ uint32_t gather_per_slot() {            // CRA_GATHER_PER_SLOT: 0 = always whole
 
 class HipEvaluator : public Evaluator {
 public:
-    explicit HipEvaluator(RiseNet* net) : net_(net) {
+    HipEvaluator(RiseNet* net, int expert_routing) : net_(net), routing_(expert_routing) {
         const RiseDesign& d = net->design();
         batch_ = d.batch;
         nb_policy_ = d.nb_policy;
@@ -66,7 +66,7 @@ public:
     const float* probs() override { return probs_; }
     void submit(int n_valid, int layout) override {
         if (record_) before_submit(n_valid, layout, false);
-        net_->submit_boards(descs_, n_valid, layout, values_, probs_, aux_);
+        net_->submit_boards(descs_, n_valid, layout, values_, probs_, aux_, routing_);
     }
     void wait() override {
         net_->wait();
@@ -78,7 +78,7 @@ public:
     const float* gathered() override { return gout_; }
     void submit_gathered(int n_valid, int layout) override {
         if (record_) before_submit(n_valid, layout, true);
-        net_->submit_boards_gathered(descs_, n_valid, layout, gidx_, gcnt_, gstride_, values_, gout_, aux_);
+        net_->submit_boards_gathered(descs_, n_valid, layout, gidx_, gcnt_, gstride_, values_, gout_, aux_, routing_);
     }
     size_t debug_replay(std::string* report) override;
 
@@ -139,6 +139,7 @@ private:
     std::vector<Record> records_;
 
     RiseNet* net_;
+    int routing_;                    // an expert set's routing for this lane's calls (mi_search_settings::expert_routing), handed over per call: the net keeps its own
     int batch_ = 0, nb_policy_ = 0;
     BoardDesc* descs_ = nullptr;
     float *values_ = nullptr, *probs_ = nullptr, *aux_ = nullptr;
@@ -214,8 +215,8 @@ size_t HipEvaluator::debug_replay(std::string* report) {
             std::memcpy(gcnt_, r.gcnt.data(), r.gcnt.size() * sizeof(uint32_t));
         }
         poison(r);
-        if (r.gathered) net_->submit_boards_gathered(descs_, r.n_valid, r.layout, gidx_, gcnt_, gstride_, values_, gout_, aux_);
-        else net_->submit_boards(descs_, r.n_valid, r.layout, values_, probs_, aux_);
+        if (r.gathered) net_->submit_boards_gathered(descs_, r.n_valid, r.layout, gidx_, gcnt_, gstride_, values_, gout_, aux_, routing_);
+        else net_->submit_boards(descs_, r.n_valid, r.layout, values_, probs_, aux_, routing_);
         net_->wait();
         std::vector<uint32_t> v, o;
         snapshot(r, v, o);
@@ -250,7 +251,10 @@ size_t HipEvaluator::debug_replay(std::string* report) {
 }
 }  // namespace
 
-std::unique_ptr<Evaluator> make_hip_evaluator(RiseNet* net) { return std::unique_ptr<Evaluator>(new HipEvaluator(net)); }
+std::unique_ptr<Evaluator> make_hip_evaluator(RiseNet* net, int expert_routing) {
+    if (expert_routing != 0 && expert_routing != 1) throw std::invalid_argument("expert routing: 0 per board, 1 majority");
+    return std::unique_ptr<Evaluator>(new HipEvaluator(net, expert_routing));
+}
 std::unique_ptr<Evaluator> make_callback_evaluator(EvalFn fn, void* user, int batch, int nb_policy) {
     return std::unique_ptr<Evaluator>(new CallbackEvaluator(fn, user, batch, nb_policy));
 }

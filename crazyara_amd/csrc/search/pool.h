@@ -42,7 +42,10 @@ public:
 };
 
 // HIP lane: RiseNet::submit_boards on the net's side stream (192 B/position H2D, planes built on the GPU, D2H of results)
-std::unique_ptr<Evaluator> make_hip_evaluator(RiseNet* net);
+// expert_routing: what a lane that holds an expert set routes by (RiseNet::Routing: 0 per board, 1 majority), handed to the net with every
+// call -- the net's own routing (mi_net_set_expert_routing: what direct calls use) is neither read nor changed; plain nets ignore it.  The
+// collector is the same either way: descriptors go in, priors and values come back per board.
+std::unique_ptr<Evaluator> make_hip_evaluator(RiseNet* net, int expert_routing = 0);
 // user-supplied lane (tests / alternative back ends): fn(user, descs, n, value, probs) fills the outputs synchronously
 typedef int (*EvalFn)(void* user, const void* descs, int n, float* value, float* probs);
 std::unique_ptr<Evaluator> make_callback_evaluator(EvalFn fn, void* user, int batch, int nb_policy);

@@ -196,6 +196,71 @@ class HipAPI:
             pass
 
 
+PHASE_LICHESS, PHASE_MOVECOUNT = 0, 1          # GamePhaseDefinition (Board::get_phase, board.cpp:540-587)
+ROUTE_PER_BOARD, ROUTE_MAJORITY = 0, 1
+
+
+def expert_dirs(model_directory: str, batch_size: int = 0, game_phase_definition: int = PHASE_LICHESS):
+    """mi_expert_dirs: the phase subdirectories of a model directory of game-phase experts, ordered by phase (host only); ValueError with
+    the library's message on every refusal."""
+    buf = C.create_string_buffer(1 << 16)
+    n = _capi.load().mi_expert_dirs(model_directory.encode(), int(batch_size), int(game_phase_definition), buf, len(buf))
+    if n < 0:
+        raise ValueError(_capi.last_error())
+    return [d for d in buf.value.decode().split("\n") if d]
+
+
+class HipExperts(HipAPI):
+    """One net per game phase behind one handle (mi_net_create_experts): every board of a batch is evaluated by the net of its own phase.
+    The reference's NeuralNetAPIUser keeps `nets` and a phase -> index map (neuralnetapiuser.cpp:34-47) and sends each mini-batch to the
+    majority phase's net; this handle takes descriptors (`submit_boards*` of the C ABI, search pools, self-play) and routes per board.
+    `predict` is refused (planes carry no phase); `predict_routed` takes the phases from the caller."""
+
+    def __init__(self, device_id: int, batch_size: int, model_directory: str, precision: str = "float16x3",
+                 game_phase_definition: int = PHASE_LICHESS, keep_logits: bool = False):
+        self._lib = _capi.load()
+        self.precision_requested = precision
+        self._h = self._lib.mi_net_create_experts(model_directory.encode(), int(device_id), int(batch_size), precision.encode(),
+                                                  int(game_phase_definition))
+        if not self._h:
+            msg = _capi.last_error()
+            raise (ValueError if "directory" in msg or "Precision" in msg or "precision" in msg or "batch" in msg else RuntimeError)(msg)
+        if keep_logits:
+            self._lib.mi_net_keep_logits(self._h, 1)
+        shape = (C.c_int * 4)()
+        npol, naux, ver, phase = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self._lib.mi_net_design(self._h, shape, C.byref(npol), C.byref(naux), C.byref(ver), C.byref(phase))
+        self.input_shape = tuple(shape)
+        self._nb_policy, self._nb_aux, self._version, self._phase = npol.value, naux.value, ver.value, phase.value
+        self.device_id = device_id
+        self.precision = precision
+        self.game_phase_definition = game_phase_definition
+
+    def get_num_phases(self) -> int:
+        return self._lib.mi_net_num_experts(self._h)
+
+    def set_routing(self, routing: int) -> None:
+        """mi_net_set_expert_routing: the routing of calls made directly on this handle; search pools hand over their settings' routing
+        with every call and leave this alone."""
+        if self._lib.mi_net_set_expert_routing(self._h, int(routing)):
+            raise ValueError(_capi.last_error())
+
+    def route_phases(self, descs, n_valid: int):
+        """mi_net_submit_boards_phases: the expert every valid board of such a call would go to (descs: address or uint8 array)."""
+        out = np.zeros(max(n_valid, 1), np.int32)
+        ptr = descs.ctypes.data if isinstance(descs, np.ndarray) else int(descs)
+        if self._lib.mi_net_submit_boards_phases(self._h, ptr, int(n_valid), out.ctypes.data_as(_capi.c_int_p)):
+            raise RuntimeError(_capi.last_error())
+        return out[:n_valid]
+
+    def predict_routed(self, input_planes, phases, value_output, prob_outputs, auxiliary_outputs=None) -> None:
+        ph = np.ascontiguousarray(phases, dtype=np.int32)
+        assert ph.size == self.get_batch_size()
+        if self._lib.mi_net_predict_routed(self._h, self._ptr(input_planes), ph.ctypes.data, self._ptr(value_output),
+                                           self._ptr(prob_outputs), self._ptr(auxiliary_outputs)):
+            raise RuntimeError(_capi.last_error())
+
+
 class NeuralNetAPIUser:
     """Owns the pinned host I/O buffers sized from the first net (neuralnetapiuser.cpp:34-75) and runs the
     `inference` benchmark loop (neuralnetapiuser.cpp:104-109)."""

@@ -150,6 +150,10 @@ int mi_pos_terminal(const mi_pos* pos);                                /* is_ter
 /* Board::get_phase (environments/chess_related/board.cpp:540-587): definition 0 = lichess (0 opening, 1 middlegame, 2 endgame; majors and
  * minors, sparse back rank, mixedness of the Divider, board.cpp:446-538), 1 = movecount (num_phases slices of a 42.85-move game); -1 on error */
 int mi_pos_game_phase(const mi_pos* pos, int num_phases, int definition);
+/* The same from a 192-byte descriptor (desc_game_phase, crazyara_amd/csrc/chess/planes.h; host and device): what an expert set routes
+ * by -- callers of the net entry points hand over descriptors, not positions.  Everything get_phase reads is in the descriptor except
+ * the game ply, whose half (total_move_cout, board.cpp:127-130) is the descriptor's fullmove - 1.  -1 on error. */
+int mi_desc_game_phase(const void* desc192, int num_phases, int definition);
 int mi_pos_number_repetitions(const mi_pos* pos);
 int mi_pos_insufficient_material(const mi_pos* pos);                  /* Board::draw_by_insufficient_material (board.cpp:175-221) */
 int mi_pos_plies_from_null(const mi_pos* pos);                        /* State::steps_from_null (boardstate.h) */
@@ -186,6 +190,43 @@ int mi_net_submit_boards(mi_net* net, const void* descs_host, int n_valid, int l
  * gathered and aux must be mi_host_alloc memory, the kernels read and write them in place.  mi_net_wait as for mi_net_submit. */
 int mi_net_submit_boards_gathered(mi_net* net, const void* descs_host, int n_valid, int layout, const unsigned short* idx,
                                   const unsigned* cnt, unsigned stride, float* value, float* gathered, float* aux);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Game-phase experts: one net per game phase behind ONE handle, every board of a batch evaluated by the net of its own phase.
+ * The reference keeps one net per phase too (fill_nn_vectors, uci/crazyara.cpp:566-600; NeuralNetAPIUser, nn/neuralnetapiuser.cpp:34-47)
+ * but sends a whole mini-batch to the net of the MAJORITY phase of its leaves (SearchThread::select_nn_index, searchthread.cpp:382-401),
+ * because one engine evaluates one batch with one set of weights.  Here the forward is one workgroup per board, so every board goes to
+ * its own expert: three launches of n_e workgroups side by side instead of one of the whole batch.
+ *
+ * model_dir holds the reference's phase subdirectories: only subdirectories whose name ends in a digit count ("phaseNone" is skipped),
+ * the digit is the phase (read_game_phase_from_string, neuralnetapi.cpp:229-239).  Refused, naming the directory: a directory that
+ * holds model files itself (a single net: mi_net_create), a phase >= the number of experts or a phase twice (NeuralNetAPIUser's two
+ * asserts) and with them a missing phase, experts that differ in input channels, policy size, aux count or version,
+ * game_phase_definition 0 (lichess) with other than three experts.  game_phase_definition: 0 lichess, 1 movecount (Board::get_phase).
+ * precision: "float16x3" exactly; every other mode and every kernel-family suffix ("-1wg", "-3k", ...) is refused by name.
+ * The handle is an ordinary mi_net: mi_net_design (the experts' common design, game_phase 0), mi_net_submit_boards,
+ * mi_net_submit_boards_gathered, mi_net_wait, mi_net_keep_logits, mi_net_device_buffers, mi_search_create / mi_search_add_lane and the
+ * self-play and arena loops take it unchanged.  mi_net_predict / mi_net_submit / mi_net_forward_device on it are refused: float planes
+ * carry no game phase; so are the per-op timing, block dump, calibration and screen hooks (the set has no launches of its own).
+ * One call at a time per handle, as on a plain net: the set keeps ONE pinned routing list that the host rewrites when a call is
+ * submitted and the kernels of that call read, so mi_net_wait comes before the next submit.  mi_expert_dirs and the constructor read
+ * every expert's model file (its design is in the file).
+ * ---------------------------------------------------------------------------------------------------------------- */
+mi_net* mi_net_create_experts(const char* model_dir, int device_id, int batch_size, const char* precision, int game_phase_definition);
+int mi_net_num_experts(const mi_net* net);               /* 0 on a plain net */
+/* discovery alone (host only, no GPU): the expert directories of model_dir ordered by phase, '\n'-separated, into out (truncated to
+ * cap); returns their number, -1 with mi_last_error on every refusal listed above */
+int mi_expert_dirs(const char* model_dir, int batch_size, int game_phase_definition, char* out, int cap);
+enum { MI_EXPERT_ROUTING_PER_BOARD = 0, MI_EXPERT_ROUTING_MAJORITY = 1 };
+/* per board (default), or the reference's rule: the whole call to the expert of the majority phase of its boards, the lowest phase
+ * among equal counts (std::max_element over the std::map of the phases that occur).  This is the routing of calls made directly
+ * (mi_net_submit_boards*, mi_net_submit_boards_phases).  The lanes of a search pool route by mi_search_settings::expert_routing, which
+ * they hand over with every call: they neither read nor change what is set here. */
+int mi_net_set_expert_routing(mi_net* net, int routing);
+/* routing only (for tests): phases_out[b] = the expert board b of such a call would go to under the set's routing */
+int mi_net_submit_boards_phases(mi_net* net, const void* descs_host, int n_valid, int* phases_out);
+/* NeuralNetAPI::predict on an expert set: the whole fixed batch of float planes, board b evaluated by expert phases[b]; blocking */
+int mi_net_predict_routed(mi_net* net, const float* in_planes, const int* phases, float* value, float* probs, float* aux);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Policy map (engine/src/environments/chess_related/outputrepresentation.cpp, policymaprepresentation.h)
@@ -227,6 +268,10 @@ typedef struct mi_search_settings {        /* SearchSettings (engine/src/agents/
      * (mctsagent.cpp:311-316, node.cpp:950-954, blazeutil.h:113-124).  Defaults 0 / 0.2 (Centi_Dirichlet_Epsilon is 25 in RL builds). */
     float dirichlet_epsilon, dirichlet_alpha;
     int version_minor;                     /* chess input representation 2.7 / 2.8 (make_version<2,7,0>, <2,8,0>); 0 otherwise */
+    /* lanes that hold an expert set (mi_net_create_experts): MI_EXPERT_ROUTING_PER_BOARD (0, default) = every leaf to the expert of
+     * its own game phase; MI_EXPERT_ROUTING_MAJORITY (1) = the reference's rule, each batch to the expert of the majority phase of its
+     * leaves (searchthread.cpp:382-410) -- there to compare results with the reference's behaviour.  Plain nets ignore it. */
+    int expert_routing;
 } mi_search_settings;
 typedef struct mi_search_stats {
     unsigned long long nodes, nn_evals, batches, simulations;
