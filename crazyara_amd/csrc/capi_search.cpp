@@ -95,8 +95,8 @@ mi_search* mi_search_create(const mi_search_settings* s, mi_net* net_a, mi_net* 
                 a = make_callback_evaluator(fn, user, fn_batch, fn_nb_policy);
             } else {
                 if (!net_a) throw std::invalid_argument("mi_search_create needs a net or an evaluator callback");
-                a = make_hip_evaluator(&net_a->net, s->expert_routing);
-                if (net_b) b = make_hip_evaluator(&net_b->net, s->expert_routing);
+                a = make_hip_evaluator(net_a->any.get(), s->expert_routing);
+                if (net_b) b = make_hip_evaluator(net_b->any.get(), s->expert_routing);
             }
             h = new mi_search;
             h->expert_routing = s->expert_routing;
@@ -110,7 +110,7 @@ mi_search* mi_search_create(const mi_search_settings* s, mi_net* net_a, mi_net* 
 
 int mi_search_add_lane(mi_search* sp, mi_net* net) {
     if (!sp || !net) { cra_set_error("null argument"); return 1; }
-    return cra_guard([&] { sp->pool->add_lane(make_hip_evaluator(&net->net, sp->expert_routing)); });
+    return cra_guard([&] { sp->pool->add_lane(make_hip_evaluator(net->any.get(), sp->expert_routing)); });
 }
 
 void mi_search_destroy(mi_search* sp) { delete sp; }

@@ -93,4 +93,23 @@ std::vector<float> default_calibration_planes(int channels, int version, int* n_
     return planes;
 }
 
+std::string int8_calibration_path(const std::string& model_file_path) { return model_file_path + ".int8calib"; }
+
+std::vector<std::pair<float, float>> read_int8_calibration(const std::string& model_file_path) {
+    std::vector<std::pair<float, float>> out;
+    std::ifstream f(int8_calibration_path(model_file_path));
+    if (!f) return out;
+    std::string magic, word;
+    int version = 0, boards = 0, blocks = 0;
+    f >> magic >> version >> word >> boards >> word >> blocks;
+    if (magic != "crazyara-int8-calibration" || version != 1 || blocks <= 0 || blocks > 4096)
+        throw std::runtime_error("malformed INT8 calibration file " + int8_calibration_path(model_file_path));
+    for (int i = 0; i < blocks; ++i) {
+        float a = 0.f, b = 0.f;
+        if (!(f >> a >> b) || !(a >= 0.f) || !(b >= 0.f)) throw std::runtime_error("malformed INT8 calibration file " + int8_calibration_path(model_file_path));
+        out.emplace_back(a, b);
+    }
+    return out;
+}
+
 }  // namespace cra

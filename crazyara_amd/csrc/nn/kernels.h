@@ -375,7 +375,7 @@ template <typename T> void launch_value_final(const ValueFinalArgs& a, hipStream
 void launch_gather_probs(const float* probs, int nb_policy, const uint16_t* idx, const uint32_t* cnt, int stride, int n_slots, float* out,
                          const float* value_dev, float* value_out, int batch, const float* aux_dev, float* aux_out, hipStream_t s);
 
-// The same for a group of a routed batch (an expert set, rise_net.hip): the expert ran its boards packed, slot w = board board_of[w] of
+// The same for a group of a routed batch (an expert set, expert_set.hip): the expert ran its boards packed, slot w = board board_of[w] of
 // the batch.  Slot w's priors go to row board_of[w] of `out`, read through that board's idx / cnt; its value and aux to that board's places.
 void launch_gather_probs_indexed(const float* probs, int nb_policy, const uint16_t* idx, const uint32_t* cnt, int stride, const int* board_of,
                                  int n_slots, float* out, const float* value_dev, float* value_out, const float* aux_dev, float* aux_out,

@@ -11,7 +11,7 @@
 #include <stdexcept>
 #include <string>
 
-#include "../nn/rise_net.h"
+#include "../nn/board_net.h"
 
 namespace cra {
 namespace search {
@@ -30,7 +30,7 @@ uint32_t gather_per_slot() {            // CRA_GATHER_PER_SLOT: 0 = always whole
 
 class HipEvaluator : public Evaluator {
 public:
-    HipEvaluator(RiseNet* net, int expert_routing) : net_(net), routing_(expert_routing) {
+    HipEvaluator(BoardNet* net, int expert_routing) : net_(net), routing_(expert_routing) {
         const RiseDesign& d = net->design();
         batch_ = d.batch;
         nb_policy_ = d.nb_policy;
@@ -138,7 +138,7 @@ private:
     bool pending_ = false;
     std::vector<Record> records_;
 
-    RiseNet* net_;
+    BoardNet* net_;
     int routing_;                    // an expert set's routing for this lane's calls (mi_search_settings::expert_routing), handed over per call: the net keeps its own
     int batch_ = 0, nb_policy_ = 0;
     BoardDesc* descs_ = nullptr;
@@ -251,7 +251,7 @@ size_t HipEvaluator::debug_replay(std::string* report) {
 }
 }  // namespace
 
-std::unique_ptr<Evaluator> make_hip_evaluator(RiseNet* net, int expert_routing) {
+std::unique_ptr<Evaluator> make_hip_evaluator(BoardNet* net, int expert_routing) {
     if (expert_routing != 0 && expert_routing != 1) throw std::invalid_argument("expert routing: 0 per board, 1 majority");
     return std::unique_ptr<Evaluator>(new HipEvaluator(net, expert_routing));
 }

@@ -12,7 +12,7 @@
 #include "mcts.h"
 
 namespace cra {
-class RiseNet;
+class BoardNet;
 namespace search {
 
 // One evaluation lane: submit() starts the evaluation of `n` descriptors and returns; wait() blocks until the
@@ -41,11 +41,12 @@ public:
     virtual size_t debug_replay(std::string* report) { (void)report; return 0; }
 };
 
-// HIP lane: RiseNet::submit_boards on the net's side stream (192 B/position H2D, planes built on the GPU, D2H of results)
-// expert_routing: what a lane that holds an expert set routes by (RiseNet::Routing: 0 per board, 1 majority), handed to the net with every
+// HIP lane: BoardNet::submit_boards (nn/board_net.h: a plain net or an expert set) on the net's side stream (192 B/position H2D, planes
+// built on the GPU, D2H of results)
+// expert_routing: what a lane that holds an expert set routes by (ExpertSet::Routing: 0 per board, 1 majority), handed to the net with every
 // call -- the net's own routing (mi_net_set_expert_routing: what direct calls use) is neither read nor changed; plain nets ignore it.  The
 // collector is the same either way: descriptors go in, priors and values come back per board.
-std::unique_ptr<Evaluator> make_hip_evaluator(RiseNet* net, int expert_routing = 0);
+std::unique_ptr<Evaluator> make_hip_evaluator(BoardNet* net, int expert_routing = 0);
 // user-supplied lane (tests / alternative back ends): fn(user, descs, n, value, probs) fills the outputs synchronously
 typedef int (*EvalFn)(void* user, const void* descs, int n, float* value, float* probs);
 std::unique_ptr<Evaluator> make_callback_evaluator(EvalFn fn, void* user, int batch, int nb_policy);

@@ -8,17 +8,12 @@
 #include <random>
 #include <thread>
 
-#include "../../crazyara_amd/csrc/nn/rise_net.h"
+#include "../../crazyara_amd/csrc/nn/board_net.h"
 #include "../../crazyara_amd/csrc/search/pool.h"
 
-// link-time stubs for the symbols pool.cpp's HIP lane references
+// link-time stubs for the symbols pool.cpp's HIP lane references (the net itself is reached through BoardNet's virtuals)
 extern "C" hipError_t hipHostMalloc(void**, size_t, unsigned) { return hipErrorNotSupported; }
 extern "C" hipError_t hipHostFree(void*) { return hipSuccess; }
-namespace cra {
-void RiseNet::submit_boards(const void*, int, int, float*, float*, float*) {}
-void RiseNet::submit_boards_gathered(const void*, int, int, const uint16_t*, const uint32_t*, uint32_t, float*, float*, float*) {}
-void RiseNet::wait() {}
-}  // namespace cra
 
 using namespace cra;
 using namespace cra::search;

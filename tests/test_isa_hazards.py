@@ -11,7 +11,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILES = ["forward", "tower", "restower", "head", "stem", "x3", "kernels", "rise_net", "block", "policy_value"]
+FILES = ["forward", "tower", "restower", "head", "stem", "x3", "kernels", "rise_net", "rise_net_build", "expert_set", "net_streams", "block", "policy_value"]
 
 
 def test_no_reader_in_the_shadow_of_an_mfma(tmp_path):

@@ -282,7 +282,7 @@ def test_nets_of_one_process_work_on_different_hardware_queues(tmp_path, hip_lib
     d = nn_cases.export_case(tmp_path, "risev2-7", cfg, sd)
     lib = _capi.load()
     monkeypatch.delenv("CRA_OWN_STREAM_PER_NET", raising=False)
-    n_queues = min(16, max(1, int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))))     # as take_net_stream() in rise_net.hip
+    n_queues = min(16, max(1, int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))))     # as take_net_stream() in net_streams.hip
     x = np.ascontiguousarray(torch.rand(8, cfg.nb_input_channels, 8, 8).numpy())
 
     def run(n):
