@@ -110,7 +110,10 @@ struct X3TowerBlock {
     // brings the expand accumulators back in front of the BN1 bias; the residual stream runs in the project weights' scale inside a block:
     // x := (x + b3) * w3_scale, + the project sums, x := x * w3_inv (powers of two: exact)
     float w1_inv, w3_scale, w3_inv;
+    int tail;                                        // 1: the upper 64 channels of the last chunk are padding (cop_pad - C_op >= 64): tower_x3_tail_kernel runs that
+                                                     // chunk at 64 channels; every other kernel ignores it.  (Fills the struct's tail padding: 96 bytes as before.)
 };
+static_assert(sizeof(X3TowerBlock) == 96, "the tower kernels index a device array of these");
 struct X3TowerArgs {
     const float* x;       // [B][64][256]
     float* y;             // [B][64][256]
@@ -120,8 +123,13 @@ struct X3TowerArgs {
     int p8;               // Precision float16p8 (tower_p8_kernel)
     int ks;               // float16p8: the depthwise size of every block of the run, 3 or 5 (0 = 3); a gated FIRST block has its gate computed in the launch
     int symmetric;        // development (CRA_X3_TOWER=symmetric when the net was made): float16x3's 3x3 runs on tower_x3_kernel, every wave all three phases
+    int no_tail;          // CRA_X3_NO_TAIL when the net was made: float16x3's two-role runs on tower_x3_roles_kernel (every chunk 128 channels), the
+                          // bit-for-bit reference of tower_x3_tail_kernel
 };
 void launch_tower_x3(const X3TowerArgs& a, hipStream_t s);
+// float16x3's two-role tower with a 64-channel last chunk in blocks whose X3TowerBlock::tail is set (x3_tail.cpp); launch_tower_x3 calls it
+void launch_tower_x3_tail(const X3TowerArgs& a, hipStream_t s);
+void init_x3_tail_kernel_attributes();
 // Small batches (round 6): ONE 3x3 bottleneck block per launch with G workgroups per board (x3.hip: block_x3_split_kernel).  Workgroup g of a
 // board stages the whole board (every workgroup needs all 256 input channels of the expand GEMM), runs the chunks [g n / G, (g + 1) n / G) of
 // the block's n = C_op / 128 chunks through expand -> depthwise -> project (float16x3 arithmetic, x3_chunks) and writes its PARTIAL project

@@ -175,6 +175,7 @@ private:
         int value_head_lds_pad = -1;    // CRA_VALUE_HEAD_LDS_PAD: kernels.h: ValueHeadArgs::lds_pad
         int value_head_variant = 0;     // CRA_VALUE_HEAD_VARIANT: kernels.h: ValueHeadArgs::variant
         bool x3_no_head_chain = false;  // CRA_X3_NO_HEAD_CHAIN: the float16x3 policy head as two launches
+        bool x3_no_tail = false;        // CRA_X3_NO_TAIL: the float16x3 two-role tower runs every chunk at 128 channels (tower_x3_roles_kernel)
         bool small_batch_heads_apart = false;   // CRA_SMALL_BATCH_HEADS_APART: a small batch's policy conv and value head as two launches
         DevSwitches();
     } dev_;

@@ -440,6 +440,7 @@ template <typename T> void RiseNet::Builder<T>::bottleneck_blocks() {
             xb.w3_inv = float(pk.w3_inv);
             xb.w3_scale = float(1.0 / pk.w3_inv);
             xb.cop_pad = cop_pad;
+            xb.tail = cop_pad - cop >= 64 ? 1 : 0;                         // the last chunk's upper half is padding (tower_x3_tail_kernel)
             if (x3_blocks.empty()) x3_run_ks = k;
             x3_blocks.push_back(xb);
         } else if (bp.family == Family::Fused) {
@@ -619,6 +620,7 @@ template <typename T> void RiseNet::Builder<T>::flush_x3_run() {
         op.tx.p8 = prec.p8() ? 1 : 0;
         op.tx.ks = x3_run_ks;
         op.tx.symmetric = dev.x3_symmetric ? 1 : 0;
+        op.tx.no_tail = dev.x3_no_tail ? 1 : 0;
         im.ops.push_back(op);
     }
     x3_blocks.clear();

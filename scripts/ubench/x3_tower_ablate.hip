@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "x3.hip"        // -I crazyara_amd/csrc/nn
+#include "x3_tail.cpp"   // tower_x3_tail_kernel, the default two-role tower (CRA_X3_NO_TAIL=1: tower_x3_roles_kernel)
 namespace cra { size_t value_head_lds_bytes(const ValueHeadArgs&) { return 0; } }      // (kernels.hip's, which this harness does not link: the head launches are not used here)
 
 #define CK(e) do { hipError_t _e = (e); if (_e != hipSuccess) { fprintf(stderr, "HIP error %s at %s\n", hipGetErrorString(_e), #e); exit(1); } } while (0)
@@ -45,6 +46,7 @@ int main(int argc, char** argv) {
         b.dwpk = upload(rec);
         b.b3 = upload(b3);
         b.cop_pad = cop_pad;
+        b.tail = cop_pad - cop >= 64 ? 1 : 0;
         b.w1_inv = 1.f;
         b.w3_scale = 1.f;
         b.w3_inv = 1.f;
@@ -63,6 +65,7 @@ int main(int argc, char** argv) {
     {   // launch_tower_x3 reads X3TowerArgs::symmetric (RiseNet::build sets it from CRA_X3_TOWER when a net is made); here it comes from the same variable
         const char* tw = getenv("CRA_X3_TOWER");
         a.symmetric = tw && std::string(tw) == "symmetric" ? 1 : 0;
+        a.no_tail = getenv("CRA_X3_NO_TAIL") != nullptr;         // (RiseNet::DevSwitches::x3_no_tail)
     }
     init_x3_kernel_attributes();
     hipStream_t s;
