@@ -130,6 +130,14 @@ void launch_tower_x3(const X3TowerArgs& a, hipStream_t s);
 // float16x3's two-role tower with a 64-channel last chunk in blocks whose X3TowerBlock::tail is set (x3_tail.cpp); launch_tower_x3 calls it
 void launch_tower_x3_tail(const X3TowerArgs& a, hipStream_t s);
 void init_x3_tail_kernel_attributes();
+// Kernel family "-wblock" (x3_wblock.cpp: block_x3w_kernel<C, KS>): block_x3_kernel's sibling for trunk widths 128 / 192 / 224 with a 3x3 or
+// 5x5 depthwise, float16x3 arithmetic.  BlockArgs as launch_block_x3 takes them, except that cop_pad is a multiple of 64 (a last chunk of
+// 64 channels runs as such) and dwpk holds the 3x3 or the 5x5 records (pack.cpp: pack_x3_depthwise_records).  launch_se_gate_w: the SE gate
+// from a block's channel sums (BlockArgs::pool_out) at any width up to 512, se_kernel's arithmetic.
+bool block_x3w_supports(int C, int ks);
+void launch_block_x3w(const BlockArgs& a, hipStream_t s);
+void init_x3_wblock_kernel_attributes();
+void launch_se_gate_w(const float* pool, float* gate, int kind, const float* w1t, const float* w2t, const float* b1, int batch, int C, hipStream_t s);
 // Small batches (round 6): ONE 3x3 bottleneck block per launch with G workgroups per board (x3.hip: block_x3_split_kernel).  Workgroup g of a
 // board stages the whole board (every workgroup needs all 256 input channels of the expand GEMM), runs the chunks [g n / G, (g + 1) n / G) of
 // the block's n = C_op / 128 chunks through expand -> depthwise -> project (float16x3 arithmetic, x3_chunks) and writes its PARTIAL project

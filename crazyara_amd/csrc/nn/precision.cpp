@@ -48,6 +48,7 @@ Precision parse_precision(const std::string& precision) {
     if (strip("-1wg")) v.board_split = false;
     if (strip("-1b")) v.boards_per_wg = 1;
     else if (strip("-2b")) v.boards_per_wg = 2;
+    if (strip("-wblock")) v.wblock = true;    // one-launch blocks at trunk widths 128 / 192 / 224 (x3_wblock.cpp); which blocks qualify is the builder's business
     if (strip("-unfused")) v.fused = v.tower = false;
     else if (strip("-perblock")) v.tower = false;
     using M = Precision::Mode;
@@ -69,6 +70,8 @@ Precision parse_precision(const std::string& precision) {
     for (const auto& m : kModes)
         if (prec == m.first) {
             v.mode = m.second;
+            if (v.wblock && !v.x3()) throw std::invalid_argument("`-wblock` is a float16x3 kernel family (float16x3-wblock | float16p8-wblock), got '" + precision + "'");
+            if (v.wblock && !v.fused) throw std::invalid_argument("`-wblock` and `-unfused` exclude each other, got '" + precision + "'");
             return v;
         }
     throw std::invalid_argument("unsupported precision '" + precision + "' (float16 | float16x3 | float16p8 | float32 | fp8 | int8)");

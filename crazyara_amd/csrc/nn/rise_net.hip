@@ -152,6 +152,12 @@ template <typename T> void RiseNet::launch_op(int i, hipStream_t s, ForwardCall&
             if (prec_.x3()) launch_block_x3(op.blk, s);
             else launch_block<T>(op.blk, s);
             break;
+        case OpKind::BlockX3W: {
+            BlockArgs a = op.blk;
+            a.batch = B;
+            launch_block_x3w(a, s);
+            break;
+        }
         case OpKind::ValueFinal: {
             ValueFinalArgs v = op.vf;
             v.value = value;
@@ -211,7 +217,8 @@ template <typename T> void RiseNet::launch_op(int i, hipStream_t s, ForwardCall&
             break;
         }
         case OpKind::SEGate:
-            launch_se_gate(static_cast<const float*>(op.x), static_cast<float*>(op.y), op.se_kind, op.w0, op.w1, op.b0, B, op.C, s);
+            if (op.C == 256) launch_se_gate(static_cast<const float*>(op.x), static_cast<float*>(op.y), op.se_kind, op.w0, op.w1, op.b0, B, op.C, s);
+            else launch_se_gate_w(static_cast<const float*>(op.x), static_cast<float*>(op.y), op.se_kind, op.w0, op.w1, op.b0, B, op.C, s);
             break;
     }
 }
@@ -246,6 +253,7 @@ const char* RiseNet::op_name(int i) const {
         case OpKind::X3SplitFinish: return "x3_split_finish";
         case OpKind::HeadsSmall: return "heads_small";
         case OpKind::Attention: return "attention";
+        case OpKind::BlockX3W: return "block_x3w";
     }
     return "?";
 }

@@ -18,6 +18,7 @@ enum class Family {
     X3Tower,   // float16x3 / float16p8: a run of 3x3 or of 5x5 blocks in one launch (x3.hip: tower_x3_kernel, tower_p8_kernel)
     X3Split,   // float16x3 / float16p8 at small batches: a 3x3 block per launch over several workgroups per board (block_x3_split_kernel)
     Fused,     // one launch per block (kernels.hip: block_kernel; x3.hip: block_x3_kernel)
+    WBlock,    // float16x3 / float16p8 with "-wblock" at 128 / 192 / 224 channels: one launch per block (x3_wblock.cpp: block_x3w_kernel)
     Layers,    // expand, depthwise and project as three layer launches
     Transformer   // a NextViT transformer block: conv GEMMs and the attention kernel (Builder::transformer_block)
 };
@@ -54,6 +55,7 @@ template <typename T> struct RiseNet::Builder {
     float *se_pool = nullptr, *se_gate = nullptr;
     const float* pending_gate = nullptr;
     int prod_op = -1;                 // last op that produced the residual stream and can emit its channel sums
+    int wblock_ops = 0;               // blocks that "-wblock" put on block_x3w_kernel (none: the precision is refused)
     double macs = 0;
     std::vector<TowerBlockDesc> tower_blocks;
     TowerStreams tower_streams;
@@ -185,6 +187,8 @@ template <typename T> void RiseNet::Builder<T>::read_model() {
 template <typename T> BlockPlan RiseNet::Builder<T>::plan(size_t i) const {
     const int k = ks[i];
     if (ntb[i]) return {Family::Transformer, false};
+    // "-wblock": every other block of a 128 / 192 / 224-channel net, also between transformer blocks; the gate comes from the launches in front
+    if (prec.wblock && prec.x3() && !dense_blocks && block_x3w_supports(C, k)) return {Family::WBlock, false};
     if (tower_ok) return {Family::Tower, i > 0};          // 3x3 and 5x5 blocks in one run; the run's first gate comes from an SE launch
     if (x3_tower) {
         // the 5x5 blocks (RISEv3.3) run in tower launches of their own (tower_*_kernel<5>); small batches run 3x3 blocks split-board (float16x3
@@ -406,7 +410,7 @@ template <typename T> void RiseNet::Builder<T>::bottleneck_blocks() {
             if (se.kind == 1) xb.se_w2t = im.upload(pk.second);
             else xb.se_b = im.upload(se.b);
         } else if (se.kind) {
-            add_se(se_op(se), bp.family == Family::Fused);
+            add_se(se_op(se), bp.family == Family::Fused || bp.family == Family::WBlock);
         }
         macs += se.macs;
         if (bp.family == Family::Tower) {
@@ -469,6 +473,31 @@ template <typename T> void RiseNet::Builder<T>::bottleneck_blocks() {
             pending_gate = nullptr;
             prod_op = int(im.ops.size());
             im.ops.push_back(op);
+            std::swap(cur, nxt);
+        } else if (bp.family == Family::WBlock) {
+            // block_x3w_kernel: C_op padded to 64 (a last chunk of 64 channels runs as such), float16x3 images in both modes
+            const int cop_pad = round_up(cop, 64);
+            const X3BlockPack pk = pack_x3_block(fold_block(nf, p), C, cop, k, cop_pad, false);
+            Op op;
+            op.kind = OpKind::BlockX3W;
+            BlockArgs& ba = op.blk;
+            ba.x = cur;
+            ba.y = nxt;
+            ba.w1pk = im.upload(pk.w1.hi);
+            ba.w1pk_lo = im.upload(pk.w1.lo);
+            ba.w3pk = im.upload(pk.w3.hi);
+            ba.w3pk_lo = im.upload(pk.w3.lo);
+            ba.dwpk = im.upload(pk.dw);
+            ba.b3 = im.upload(pk.b3);
+            ba.batch = B;
+            ba.C = C;
+            ba.cop_pad = cop_pad;
+            ba.ks = k;
+            ba.gate = pending_gate;
+            pending_gate = nullptr;
+            prod_op = int(im.ops.size());
+            im.ops.push_back(op);
+            ++wblock_ops;
             std::swap(cur, nxt);
         } else {
             add_conv(p + ".body.0", p + ".body.1", cur, e, nullptr, C, C, cop, 1, true, nullptr);   // 1x1 expand + BN + ReLU
@@ -872,6 +901,10 @@ template <typename T> void RiseNet::build(const NetFile& nf) {
     if (b.dense_blocks && b.tower_ok) b.dense_tower();
     else if (b.dense_blocks) b.dense_layer_blocks();
     else b.bottleneck_blocks();
+    if (prec_.wblock && b.wblock_ops == 0)
+        throw std::runtime_error("`-wblock` runs the mobile-bottleneck blocks of 128 / 192 / 224-channel nets in one launch each: no block of this model qualifies (" +
+                                 std::to_string(b.C) + " channels, " + (b.dense_blocks ? "dense residual blocks" : "mobile-bottleneck blocks") +
+                                 "); use the precision without the suffix");
     if (b.head_ok) {
         b.one_launch_head();
     } else {
@@ -882,6 +915,7 @@ template <typename T> void RiseNet::build(const NetFile& nf) {
     }
     init_block_kernel_attributes<T>();
     init_x3_kernel_attributes();
+    init_x3_wblock_kernel_attributes();
     init_tower_kernel_attributes();
     init_restower_kernel_attributes();
     init_head_kernel_attributes();

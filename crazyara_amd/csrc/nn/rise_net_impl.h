@@ -18,7 +18,7 @@ namespace cra {
             throw std::runtime_error(std::string("HIP error ") + hipGetErrorString(_e) + " at " #expr);      \
     } while (0)
 
-enum class OpKind { PlanesToAct, Conv, Depthwise, SE, ValueHead, Softmax, Block, ValueFinal, SEGate, Tower, Head, Stem, ResTower, Forward, TowerX3, BlockX3Split, X3SplitFinish, HeadsSmall, Attention };
+enum class OpKind { PlanesToAct, Conv, Depthwise, SE, ValueHead, Softmax, Block, ValueFinal, SEGate, Tower, Head, Stem, ResTower, Forward, TowerX3, BlockX3Split, X3SplitFinish, HeadsSmall, Attention, BlockX3W };
 
 struct Op {
     OpKind kind;
@@ -31,7 +31,7 @@ struct Op {
     const float *w0 = nullptr, *w1 = nullptr, *b0 = nullptr;
     int C = 0, ks = 0, se_kind = 0;
     ValueHeadArgs vh{};
-    BlockArgs blk{};
+    BlockArgs blk{};              // Block; BlockX3W (x3_wblock.cpp)
     ValueFinalArgs vf{};
     TowerArgs tw{};
     HeadArgs hd{};

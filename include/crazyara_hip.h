@@ -48,7 +48,10 @@ typedef struct mi_net mi_net;
  * reference's option, TensorRT INT8 with a calibration cache, tensorrtapi.cpp:229-248 -- is accepted as a name for it): float16 with OCP
  * e4m3 operands in the two GEMMs of every residual block (f32 accumulation, per-row power-of-two weight scales, no calibration file; the
  * residual stream, stem and heads stay f16).  256-channel bottleneck (RISE) nets only; error against fp32 about 2^7 times float16's
- * (DESIGN 4.3).  Other models: RuntimeError, as an unsupported precision is in the reference. */
+ * (DESIGN 4.3).  Other models: RuntimeError, as an unsupported precision is in the reference.
+ * Suffix "-wblock" on "float16x3" / "float16p8" ("float16x3-wblock"): nets of 128, 192 or 224 channels (AlphaVile) run every mobile-bottleneck
+ * block that is not a transformer block in one launch instead of three; opt-in, the same arithmetic in another f32 summation
+ * order.  Refused on every other precision and on a net none of whose blocks qualifies (256 channels, dense block families, other widths). */
 mi_net* mi_net_create(const char* model_dir, int device_id, int batch_size, const char* precision);
 /* Precision "int8" -- the reference's calibrated INT8 mode (TensorRT INT8 with an Int8EntropyCalibrator2 over the engine's
  * ChessBatchStream positions, engine/src/nn/tensorrtapi.cpp:334-360, environments/chess_related/chessbatchstream.cpp:44-94) -- needs one

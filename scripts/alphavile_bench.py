@@ -3,6 +3,9 @@ float32, and time_ops per op so that the attention launch's share of the forward
 on them).  One JSON line per (size, precision) on stdout; --ops also prints the per-op table.
 
     python scripts/alphavile_bench.py [--batch 256] [--iters 50] [--sizes tiny,small,normal,large] [--precisions float16x3,float16,float32] [--ops]
+
+A/B of the one-launch blocks: --precisions float16x3,float16x3-wblock,float16x3,float16x3-wblock,... (a precision may repeat: the runs of a
+size then interleave in one process).
 """
 import argparse
 import json
