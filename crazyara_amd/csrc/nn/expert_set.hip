@@ -108,9 +108,9 @@ ExpertSet::ExpertSet(const std::string& model_dir, int device_id, int batch_size
     : BoardNet(device_id) {
     if (batch_size <= 0) throw std::invalid_argument("batch size must be positive");
     const Precision prec = parse_precision(precision);
-    // (every kernel-family suffix too: "-1wg", "-3k", "-8w", "-1b" / "-2b", "-unfused", "-perblock", "-wblock" are variants no routed call was checked in)
+    // (every kernel-family suffix too: "-1wg", "-3k", "-8w", "-1b" / "-2b", "-unfused", "-perblock", "-wblock", "-wnet" are variants no routed call was checked in)
     if (prec.mode != Precision::Mode::Float16x3 || !prec.fused || !prec.tower || !prec.one_launch || prec.thin_waves || !prec.board_split || prec.boards_per_wg != 0 ||
-        prec.wblock)
+        prec.wblock || prec.wnet)
         throw std::invalid_argument("an expert set runs Precision float16x3 (got '" + precision + "'): the routed forward is checked bit for bit in that mode only");
     const std::vector<ExpertDir> dirs = discover_experts(model_dir, batch_size, game_phase_definition);      // host only: refusals come before the device is touched
     phase_definition_ = game_phase_definition;

@@ -138,6 +138,24 @@ bool block_x3w_supports(int C, int ks);
 void launch_block_x3w(const BlockArgs& a, hipStream_t s);
 void init_x3_wblock_kernel_attributes();
 void launch_se_gate_w(const float* pool, float* gate, int kind, const float* w1t, const float* w2t, const float* b1, int batch, int C, hipStream_t s);
+// Kernel family "-wnet" (x3_wntb.cpp: ntb_x3w_kernel<C>): a NextViT transformer block of a 128 / 192 / 224-channel net in one launch, float16x3
+// arithmetic, the bits of the nine layer launches (RiseNet::Builder::transformer_block).  Every layer's weights are the hi / lo fragment
+// images of pack_dense_split (pack.cpp: pack_x3_ntb; the grouped 3x3 as [cout tile][tap] fragments of its 32-channel groups) and its
+// bias [cout] floats.  ntb_x3w_supports: the widths of rise_config.ntb_widths, (C, D, M, H) = (128, 96, 32, 256), (192, 160, 32, 384),
+// (224, 160, 64, 448).
+struct NtbLayer {
+    const void *wh, *wl;
+    const float* bias;
+};
+struct NtbArgs {
+    const float* x;       // [B][64][C]
+    float* y;             // [B][64][C] (may be x)
+    int batch, C, D, M, H;
+    NtbLayer patch, qkv, proj, projection, mhca, mhca_proj, mlp1, mlp2;
+};
+bool ntb_x3w_supports(int C, int D, int M, int H);
+void launch_ntb_x3w(const NtbArgs& a, hipStream_t s);
+void init_x3_wntb_kernel_attributes();
 // Small batches (round 6): ONE 3x3 bottleneck block per launch with G workgroups per board (x3.hip: block_x3_split_kernel).  Workgroup g of a
 // board stages the whole board (every workgroup needs all 256 input channels of the expand GEMM), runs the chunks [g n / G, (g + 1) n / G) of
 // the block's n = C_op / 128 chunks through expand -> depthwise -> project (float16x3 arithmetic, x3_chunks) and writes its PARTIAL project

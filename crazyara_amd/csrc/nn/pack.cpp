@@ -518,6 +518,27 @@ TowerImage close_tower_streams(TowerStreams r, bool fp8) {
     return out;
 }
 
+X3NtbPack pack_x3_ntb(const NtbFold& n) {
+    const int C = n.C, D = n.D, M = n.M, H = n.H;
+    if (D % 32 != 0 || M % 32 != 0 || H % 32 != 0 || C != D + M) throw std::runtime_error("pack_x3_ntb: widths must be multiples of 32");
+    X3NtbPack out;
+    out.patch = pack_dense_split(n.patch, D, C, 1, D, C);
+    out.qkv = pack_dense_split(n.qkv, 3 * D, D, 1, 3 * D, D);
+    out.proj = pack_dense_split(n.proj, D, D, 1, D, D);
+    out.projection = pack_dense_split(n.projection, M, D, 1, M, D);
+    Folded g;                                                 // the diagonal blocks of fold_ntb's dense image: [M][32][3][3]
+    g.b = n.mhca.b;
+    g.w.resize(size_t(M) * 32 * 9);
+    for (int co = 0; co < M; ++co)
+        for (int j = 0; j < 32; ++j)
+            for (int t = 0; t < 9; ++t) g.w[(size_t(co) * 32 + j) * 9 + t] = n.mhca.w[(size_t(co) * M + (co / 32) * 32 + j) * 9 + t];
+    out.mhca = pack_dense_split(g, M, 32, 3, M, 32);
+    out.mhca_proj = pack_dense_split(n.mhca_proj, M, M, 1, M, M);
+    out.mlp1 = pack_dense_split(n.mlp1, H, C, 1, H, C);
+    out.mlp2 = pack_dense_split(n.mlp2, C, H, 1, C, H);
+    return out;
+}
+
 X3BlockPack pack_x3_block(const BlockFold& bf, int C, int cop, int k, int cop_pad, bool p8) {
     X3BlockPack out;
     out.w1 = p8 ? pack_dense_p8(bf.expand, cop, C, 1, cop_pad, C, &out.w1_inv) : pack_dense_split(bf.expand, cop, C, 1, cop_pad, C);

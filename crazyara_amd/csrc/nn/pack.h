@@ -103,6 +103,12 @@ struct X3BlockPack {
 };
 X3BlockPack pack_x3_block(const BlockFold& bf, int C, int cop, int k, int cop_pad, bool p8);
 
+// Precision float16x3 / float16p8, "-wnet": an NTB's images for ntb_x3w_kernel (x3_wntb.cpp, kernels.h: NtbArgs).  Every 1x1 layer is the
+// fragment image the layer conv reads ([cout tile][k-slab], pack_dense_split); the grouped 3x3 holds its groups only, [cout tile][tap]
+// fragments over the 32 input channels of the tile's group.
+struct X3NtbPack { SplitPack patch, qkv, proj, projection, mhca, mhca_proj, mlp1, mlp2; };
+X3NtbPack pack_x3_ntb(const NtbFold& n);
+
 // SE weights of block `prefix`: kind 0 none, 1 ca_se (w0 = FC1^T [C][C/2], w1 = FC2^T [C/2][C]), 2 eca_se (w0 = centre tap^T [C][C],
 // b = bias); the layout of the SE / SE-gate kernels.  Throws on an unknown type.
 struct SEWeights {

@@ -31,6 +31,8 @@ struct Precision {
     bool board_split = true;   // float16x3 / float16p8 small batches run split-board blocks ("-1wg": one workgroup per board)
     bool wblock = false;       // "-wblock": float16x3 / float16p8 nets of 128 / 192 / 224 channels run their mobile-bottleneck blocks one launch each
                                // (x3_wblock.cpp: block_x3w_kernel) instead of three layer launches; opt-in, refused where no block qualifies
+    bool wnet = false;         // "-wnet": "-wblock" (implied) plus every NextViT transformer block of such a net in one launch (x3_wntb.cpp:
+                               // ntb_x3w_kernel) instead of nine; opt-in
     int boards_per_wg = 0;     // dense residual tower: 0 = by batch size (2 from 512 boards), 1 / 2 = forced ("-1b" / "-2b")
     bool fp16() const { return mode == Mode::Float16 || mode == Mode::Fp8 || mode == Mode::Int8; }   // f16 activations (else float)
     bool x3() const { return mode == Mode::Float16x3 || mode == Mode::Float16p8; }    // split-operand f16 MFMAs (x3.hip)
@@ -51,7 +53,8 @@ public:
     //            or "float32" (exact f32 MFMA); float16 runs the residual tower kernel (tower.hip: runs of 3x3 blocks in one launch);
     //            suffix "-perblock" selects one fused launch per bottleneck block, "-unfused" the layer-granular kernels
     //            (both kept for A/B measurements and as independent implementations in the parity tests); "-wblock" on float16x3 /
-    //            float16p8 runs the mobile-bottleneck blocks of a 128 / 192 / 224-channel net (AlphaVile) one launch each.   Throws std::invalid_argument / std::runtime_error.
+    //            float16p8 runs the mobile-bottleneck blocks of a 128 / 192 / 224-channel net (AlphaVile) one launch each, "-wnet" its
+    //            transformer blocks too.   Throws std::invalid_argument / std::runtime_error.
     RiseNet(const std::string& model_path, int device_id, int batch_size, const std::string& precision) : RiseNet(model_path, device_id, batch_size, precision, nullptr) {}
     ~RiseNet() override;
 

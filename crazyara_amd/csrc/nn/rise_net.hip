@@ -158,6 +158,12 @@ template <typename T> void RiseNet::launch_op(int i, hipStream_t s, ForwardCall&
             launch_block_x3w(a, s);
             break;
         }
+        case OpKind::NtbX3W: {
+            NtbArgs a = op.ntb;
+            a.batch = B;
+            launch_ntb_x3w(a, s);
+            break;
+        }
         case OpKind::ValueFinal: {
             ValueFinalArgs v = op.vf;
             v.value = value;
@@ -254,6 +260,7 @@ const char* RiseNet::op_name(int i) const {
         case OpKind::HeadsSmall: return "heads_small";
         case OpKind::Attention: return "attention";
         case OpKind::BlockX3W: return "block_x3w";
+        case OpKind::NtbX3W: return "ntb_x3w";
     }
     return "?";
 }

@@ -20,7 +20,8 @@ enum class Family {
     Fused,     // one launch per block (kernels.hip: block_kernel; x3.hip: block_x3_kernel)
     WBlock,    // float16x3 / float16p8 with "-wblock" at 128 / 192 / 224 channels: one launch per block (x3_wblock.cpp: block_x3w_kernel)
     Layers,    // expand, depthwise and project as three layer launches
-    Transformer   // a NextViT transformer block: conv GEMMs and the attention kernel (Builder::transformer_block)
+    Transformer,  // a NextViT transformer block: conv GEMMs and the attention kernel (Builder::transformer_block)
+    WNtb       // float16x3 / float16p8 with "-wnet": a transformer block of rise_config.ntb_widths in one launch (x3_wntb.cpp: ntb_x3w_kernel)
 };
 struct BlockPlan {
     Family family;
@@ -56,6 +57,7 @@ template <typename T> struct RiseNet::Builder {
     const float* pending_gate = nullptr;
     int prod_op = -1;                 // last op that produced the residual stream and can emit its channel sums
     int wblock_ops = 0;               // blocks that "-wblock" put on block_x3w_kernel (none: the precision is refused)
+    int wntb_ops = 0;                 // transformer blocks that "-wnet" put on ntb_x3w_kernel
     double macs = 0;
     std::vector<TowerBlockDesc> tower_blocks;
     TowerStreams tower_streams;
@@ -81,6 +83,7 @@ template <typename T> struct RiseNet::Builder {
     void dense_layer_blocks();
     void bottleneck_blocks();
     void transformer_block(size_t i);
+    void transformer_block_x3w(const NtbFold& n);
     void flush_tower();
     void flush_x3_run();
     void one_launch_head();
@@ -186,7 +189,16 @@ template <typename T> void RiseNet::Builder<T>::read_model() {
 // the one place that decides which family runs bottleneck block i and where its SE gate is computed
 template <typename T> BlockPlan RiseNet::Builder<T>::plan(size_t i) const {
     const int k = ks[i];
-    if (ntb[i]) return {Family::Transformer, false};
+    if (ntb[i]) {
+        if (prec.wnet && prec.x3()) {                        // "-wnet": the widths ntb_x3w_kernel is made for; any other NTB keeps its nine launches
+            const std::string p = "body_spatial." + std::to_string(i + 1);
+            if (nf.has(p + ".patch_embed.conv.weight") && nf.has(p + ".mlp.conv1.weight")) {
+                const int D = int(nf.get(p + ".patch_embed.conv.weight").shape[0]), H = int(nf.get(p + ".mlp.conv1.weight").shape[0]);
+                if (ntb_x3w_supports(C, D, C - D, H)) return {Family::WNtb, false};
+            }
+        }
+        return {Family::Transformer, false};
+    }
     // "-wblock": every other block of a 128 / 192 / 224-channel net, also between transformer blocks; the gate comes from the launches in front
     if (prec.wblock && prec.x3() && !dense_blocks && block_x3w_supports(C, k)) return {Family::WBlock, false};
     if (tower_ok) return {Family::Tower, i > 0};          // 3x3 and 5x5 blocks in one run; the run's first gate comes from an SE launch
@@ -388,8 +400,9 @@ template <typename T> void RiseNet::Builder<T>::bottleneck_blocks() {
         const std::string p = "body_spatial." + std::to_string(i + 1);
         const int cop = cops[i], k = ks[i];
         const BlockPlan bp = plan(i);
-        if (bp.family == Family::Transformer) {
-            transformer_block(i);
+        if (bp.family == Family::Transformer || bp.family == Family::WNtb) {
+            if (bp.family == Family::WNtb) transformer_block_x3w(fold_ntb(nf, p, C));
+            else transformer_block(i);
             continue;
         }
         const bool x3_family = bp.family == Family::X3Tower || bp.family == Family::X3Split;
@@ -570,6 +583,36 @@ template <typename T> void RiseNet::Builder<T>::transformer_block(size_t i) {
     conv_op(n.mlp2, e, cur, H, H, C, 1, 0).resid = xs;
     macs += n.macs;
     prod_op = -1;
+}
+
+// NTB in one launch ("-wnet", x3_wntb.cpp): fold_ntb's layers as ntb_x3w_kernel's images; cur -> nxt.  Like the layer form it emits no
+// channel sums: a gated block behind it takes its squeeze from an SE launch.
+template <typename T> void RiseNet::Builder<T>::transformer_block_x3w(const NtbFold& n) {
+    const X3NtbPack pk = pack_x3_ntb(n);
+    Op op;
+    op.kind = OpKind::NtbX3W;
+    NtbArgs& a = op.ntb;
+    a.x = reinterpret_cast<const float*>(cur);
+    a.y = reinterpret_cast<float*>(nxt);
+    a.batch = B;
+    a.C = C;
+    a.D = n.D;
+    a.M = n.M;
+    a.H = n.H;
+    auto layer = [&](const SplitPack& sp, const Folded& fd, int co) { return NtbLayer{im.upload(sp.hi), im.upload(sp.lo), im.upload_d2f(fd.b, size_t(co))}; };
+    a.patch = layer(pk.patch, n.patch, n.D);
+    a.qkv = layer(pk.qkv, n.qkv, 3 * n.D);
+    a.proj = layer(pk.proj, n.proj, n.D);
+    a.projection = layer(pk.projection, n.projection, n.M);
+    a.mhca = layer(pk.mhca, n.mhca, n.M);
+    a.mhca_proj = layer(pk.mhca_proj, n.mhca_proj, n.M);
+    a.mlp1 = layer(pk.mlp1, n.mlp1, n.H);
+    a.mlp2 = layer(pk.mlp2, n.mlp2, C);
+    im.ops.push_back(op);
+    macs += n.macs;
+    ++wntb_ops;
+    prod_op = -1;
+    std::swap(cur, nxt);
 }
 
 template <typename T> void RiseNet::Builder<T>::flush_tower() {
@@ -901,7 +944,11 @@ template <typename T> void RiseNet::build(const NetFile& nf) {
     if (b.dense_blocks && b.tower_ok) b.dense_tower();
     else if (b.dense_blocks) b.dense_layer_blocks();
     else b.bottleneck_blocks();
-    if (prec_.wblock && b.wblock_ops == 0)
+    if (prec_.wnet && b.wblock_ops == 0 && b.wntb_ops == 0)
+        throw std::runtime_error("`-wnet` runs the mobile-bottleneck and transformer blocks of 128 / 192 / 224-channel nets in one launch each: no block of this model qualifies (" +
+                                 std::to_string(b.C) + " channels, " + (b.dense_blocks ? "dense residual blocks" : "mobile-bottleneck blocks") +
+                                 "); use the precision without the suffix");
+    if (prec_.wblock && !prec_.wnet && b.wblock_ops == 0)
         throw std::runtime_error("`-wblock` runs the mobile-bottleneck blocks of 128 / 192 / 224-channel nets in one launch each: no block of this model qualifies (" +
                                  std::to_string(b.C) + " channels, " + (b.dense_blocks ? "dense residual blocks" : "mobile-bottleneck blocks") +
                                  "); use the precision without the suffix");
@@ -916,6 +963,7 @@ template <typename T> void RiseNet::build(const NetFile& nf) {
     init_block_kernel_attributes<T>();
     init_x3_kernel_attributes();
     init_x3_wblock_kernel_attributes();
+    init_x3_wntb_kernel_attributes();
     init_tower_kernel_attributes();
     init_restower_kernel_attributes();
     init_head_kernel_attributes();

@@ -18,7 +18,7 @@ namespace cra {
             throw std::runtime_error(std::string("HIP error ") + hipGetErrorString(_e) + " at " #expr);      \
     } while (0)
 
-enum class OpKind { PlanesToAct, Conv, Depthwise, SE, ValueHead, Softmax, Block, ValueFinal, SEGate, Tower, Head, Stem, ResTower, Forward, TowerX3, BlockX3Split, X3SplitFinish, HeadsSmall, Attention, BlockX3W };
+enum class OpKind { PlanesToAct, Conv, Depthwise, SE, ValueHead, Softmax, Block, ValueFinal, SEGate, Tower, Head, Stem, ResTower, Forward, TowerX3, BlockX3Split, X3SplitFinish, HeadsSmall, Attention, BlockX3W, NtbX3W };
 
 struct Op {
     OpKind kind;
@@ -32,6 +32,7 @@ struct Op {
     int C = 0, ks = 0, se_kind = 0;
     ValueHeadArgs vh{};
     BlockArgs blk{};              // Block; BlockX3W (x3_wblock.cpp)
+    NtbArgs ntb{};                // NtbX3W (x3_wntb.cpp)
     ValueFinalArgs vf{};
     TowerArgs tw{};
     HeadArgs hd{};

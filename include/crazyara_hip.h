@@ -51,7 +51,10 @@ typedef struct mi_net mi_net;
  * (DESIGN 4.3).  Other models: RuntimeError, as an unsupported precision is in the reference.
  * Suffix "-wblock" on "float16x3" / "float16p8" ("float16x3-wblock"): nets of 128, 192 or 224 channels (AlphaVile) run every mobile-bottleneck
  * block that is not a transformer block in one launch instead of three; opt-in, the same arithmetic in another f32 summation
- * order.  Refused on every other precision and on a net none of whose blocks qualifies (256 channels, dense block families, other widths). */
+ * order.  Refused on every other precision and on a net none of whose blocks qualifies (256 channels, dense block families, other widths).
+ * Suffix "-wnet" ("float16x3-wnet", "float16p8-wnet"): everything "-wblock" means, and every NextViT transformer block of such a net
+ * (C = 128 / 192 / 224 with E_MHSA widths 96 / 160 / 160 and an Mlp of 2 C) runs in one launch instead of nine, the same bits as the nine
+ * (DESIGN 9a); a transformer block of another shape keeps its launches.  Opt-in; refused like "-wblock", and by expert sets. */
 mi_net* mi_net_create(const char* model_dir, int device_id, int batch_size, const char* precision);
 /* Precision "int8" -- the reference's calibrated INT8 mode (TensorRT INT8 with an Int8EntropyCalibrator2 over the engine's
  * ChessBatchStream positions, engine/src/nn/tensorrtapi.cpp:334-360, environments/chess_related/chessbatchstream.cpp:44-94) -- needs one

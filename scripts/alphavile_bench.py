@@ -5,7 +5,8 @@ on them).  One JSON line per (size, precision) on stdout; --ops also prints the 
     python scripts/alphavile_bench.py [--batch 256] [--iters 50] [--sizes tiny,small,normal,large] [--precisions float16x3,float16,float32] [--ops]
 
 A/B of the one-launch blocks: --precisions float16x3,float16x3-wblock,float16x3,float16x3-wblock,... (a precision may repeat: the runs of a
-size then interleave in one process).
+size then interleave in one process); of the one-launch transformer blocks: float16x3-wblock,float16x3-wnet,...  ntb_ms is the time of a
+net's transformer blocks: the ntb_x3w ops, or the nine layer ops of every attention launch (four before it, four behind).
 """
 import argparse
 import json
@@ -53,9 +54,11 @@ def main():
             ops = net.time_ops(max(1, args.iters // 5))
             total = sum(t for _, t in ops)
             att = sum(t for n, t in ops if n == "attention")
+            names = [n for n, _ in ops]
+            ntb = sum(t for n, t in ops if n == "ntb_x3w") + sum(sum(t for _, t in ops[i - 2:i + 7]) for i, n in enumerate(names) if n == "attention")
             rec = dict(net=f"alphavile-{size}", precision=prec, batch=B, forward_ms=ms, predict_ms=round(predict_ms, 4),
                        evals_per_s=round(B / ((ms if ms else predict_ms) * 1e-3)), launches=len(ops),
-                       ops_ms_sum=round(total, 4), attention_ms=round(att, 4), attention_share=round(att / total, 4),
+                       ops_ms_sum=round(total, 4), attention_ms=round(att, 4), attention_share=round(att / total, 4), ntb_ms=round(ntb, 4),
                        mflop_per_board=round(net.flops_per_position() / 1e6, 1))
             print(json.dumps(rec), flush=True)
             if args.ops:
