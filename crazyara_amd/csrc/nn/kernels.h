@@ -138,6 +138,26 @@ bool block_x3w_supports(int C, int ks);
 void launch_block_x3w(const BlockArgs& a, hipStream_t s);
 void init_x3_wblock_kernel_attributes();
 void launch_se_gate_w(const float* pool, float* gate, int kind, const float* w1t, const float* w2t, const float* b1, int batch, int C, hipStream_t s);
+// Kernel family "-wsplit" (x3_wsplit.cpp: block_x3w_split_kernel<C, KS>): block_x3w_kernel over G workgroups per board with
+// X3SplitArgs' exchange, for nets made for few boards.  Share g of a board stages the whole board -- the sum of the gin float images the launch before
+// wrote, added in the order of their index, times blk.gate if the block is gated --, runs the chunks [g n / G, (g + 1) n / G) of the
+// block's n = x3w_split_chunks(cop_pad) chunks and stores its partial project sums as an image of its own; share 0 adds the BN3 bias and
+// the residual.  launch_x3w_split_finish adds a block's images into the float stream y [B][64][C] and, with pool_out, leaves the stream's
+// channel sums [B][C] in block_x3w_kernel's order of addition (BlockArgs::pool_out) for launch_se_gate_w.  One share gives
+// block_x3w_kernel's bits.  blk.x, blk.y and blk.pool_out are not used.
+constexpr int kX3WSplitMaxG = 8;
+struct X3WSplitArgs {
+    BlockArgs blk;            // the block as launch_block_x3w takes it; batch = the boards of the call
+    const float* x_parts;     // [B][gin][64][C]: the stream = the sum of these images (stream_in: gin = 1, the float stream itself)
+    float* y_parts;           // [B][G][64][C]
+    int gin, G;               // 1 <= gin <= kX3WSplitMaxG, 1 <= G <= min(x3w_split_chunks(cop_pad), kX3WSplitMaxG)
+    int stream_in;            // host side: x_parts is the float stream whatever the launch before wrote
+};
+int x3w_split_chunks(int cop_pad);                               // chunks of 128 channels, a 64-channel tail counted as one
+int x3w_split_shares(int cop_pad, int boards, int cu_count);     // G of a call: min(chunks, kX3WSplitMaxG, cu_count / boards), at least 1
+void launch_block_x3w_split(const X3WSplitArgs& a, hipStream_t s);
+void launch_x3w_split_finish(const float* parts, int gin, float* y, float* pool_out, int batch, int C, hipStream_t s);
+void init_x3_wsplit_kernel_attributes();
 // Kernel family "-wnet" (x3_wntb.cpp: ntb_x3w_kernel<C>): a NextViT transformer block of a 128 / 192 / 224-channel net in one launch, float16x3
 // arithmetic, the bits of the nine layer launches (RiseNet::Builder::transformer_block).  Every layer's weights are the hi / lo fragment
 // images of pack_dense_split (pack.cpp: pack_x3_ntb; the grouped 3x3 as [cout tile][tap] fragments of its 32-channel groups) and its

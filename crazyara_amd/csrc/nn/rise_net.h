@@ -33,6 +33,8 @@ struct Precision {
                                // (x3_wblock.cpp: block_x3w_kernel) instead of three layer launches; opt-in, refused where no block qualifies
     bool wnet = false;         // "-wnet": "-wblock" (implied) plus every NextViT transformer block of such a net in one launch (x3_wntb.cpp:
                                // ntb_x3w_kernel) instead of nine; opt-in
+    bool wsplit = false;       // "-wsplit": "-wnet" (implied) and, in a net made for at most kBoardSplitMaxBatch boards, every block of "-wblock" over
+                               // several workgroups per board (x3_wsplit.cpp: block_x3w_split_kernel); opt-in
     int boards_per_wg = 0;     // dense residual tower: 0 = by batch size (2 from 512 boards), 1 / 2 = forced ("-1b" / "-2b")
     bool fp16() const { return mode == Mode::Float16 || mode == Mode::Fp8 || mode == Mode::Int8; }   // f16 activations (else float)
     bool x3() const { return mode == Mode::Float16x3 || mode == Mode::Float16p8; }    // split-operand f16 MFMAs (x3.hip)
@@ -54,7 +56,8 @@ public:
     //            suffix "-perblock" selects one fused launch per bottleneck block, "-unfused" the layer-granular kernels
     //            (both kept for A/B measurements and as independent implementations in the parity tests); "-wblock" on float16x3 /
     //            float16p8 runs the mobile-bottleneck blocks of a 128 / 192 / 224-channel net (AlphaVile) one launch each, "-wnet" its
-    //            transformer blocks too.   Throws std::invalid_argument / std::runtime_error.
+    //            transformer blocks too, "-wsplit" is "-wnet" with those blocks over several workgroups per board in a net made for at
+    //            most kBoardSplitMaxBatch boards.   Throws std::invalid_argument / std::runtime_error.
     RiseNet(const std::string& model_path, int device_id, int batch_size, const std::string& precision) : RiseNet(model_path, device_id, batch_size, precision, nullptr) {}
     ~RiseNet() override;
 
@@ -141,7 +144,7 @@ private:
     struct ForwardCall {
         int boards = 0;                    // 0: the whole batch; n: a forward of n boards (every board-batched launch takes n)
         const IoOverride* io = nullptr;
-        int prev_g = 1;                    // launch_op: the workgroups per board of the BlockX3Split launch before this one
+        int prev_g = 1;                    // launch_op: the workgroups per board of the BlockX3Split / BlockX3WSplit launch before this one
     };
     // the companion net of `parent` (small_) works in the parent's stream
     RiseNet(const std::string& model_path, int device_id, int batch_size, const std::string& precision, const RiseNet* parent);

@@ -158,6 +158,20 @@ template <typename T> void RiseNet::launch_op(int i, hipStream_t s, ForwardCall&
             launch_block_x3w(a, s);
             break;
         }
+        case OpKind::BlockX3WSplit: {                              // the shares per board follow the boards of THIS forward; a launch reads as
+            X3WSplitArgs a = op.ws;                                // many images per board as the launch before it wrote
+            if (n > 0) {
+                a.blk.batch = n;
+                a.G = x3w_split_shares(a.blk.cop_pad, n, cu_count_);
+                a.gin = a.stream_in ? 1 : call.prev_g;
+                call.prev_g = a.G;
+            }
+            launch_block_x3w_split(a, s);
+            break;
+        }
+        case OpKind::X3WSplitFinish:
+            launch_x3w_split_finish(op.ws.x_parts, n > 0 ? call.prev_g : op.ws.gin, static_cast<float*>(op.ws.blk.y), op.ws.blk.pool_out, B, op.ws.blk.C, s);
+            break;
         case OpKind::NtbX3W: {
             NtbArgs a = op.ntb;
             a.batch = B;
@@ -261,6 +275,8 @@ const char* RiseNet::op_name(int i) const {
         case OpKind::Attention: return "attention";
         case OpKind::BlockX3W: return "block_x3w";
         case OpKind::NtbX3W: return "ntb_x3w";
+        case OpKind::BlockX3WSplit: return "block_x3w_split";
+        case OpKind::X3WSplitFinish: return "x3w_split_finish";
     }
     return "?";
 }

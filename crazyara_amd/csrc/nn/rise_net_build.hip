@@ -19,6 +19,8 @@ enum class Family {
     X3Split,   // float16x3 / float16p8 at small batches: a 3x3 block per launch over several workgroups per board (block_x3_split_kernel)
     Fused,     // one launch per block (kernels.hip: block_kernel; x3.hip: block_x3_kernel)
     WBlock,    // float16x3 / float16p8 with "-wblock" at 128 / 192 / 224 channels: one launch per block (x3_wblock.cpp: block_x3w_kernel)
+    WSplit,    // float16x3 / float16p8 with "-wsplit" in a net made for few boards: WBlock's blocks over several workgroups per board
+               // (x3_wsplit.cpp: block_x3w_split_kernel)
     Layers,    // expand, depthwise and project as three layer launches
     Transformer,  // a NextViT transformer block: conv GEMMs and the attention kernel (Builder::transformer_block)
     WNtb       // float16x3 / float16p8 with "-wnet": a transformer block of rise_config.ntb_widths in one launch (x3_wntb.cpp: ntb_x3w_kernel)
@@ -66,6 +68,10 @@ template <typename T> struct RiseNet::Builder {
     int x3_run_ks = 3;                // a run is all 3x3 or all 5x5 blocks (tower_x3_roles_kernel<KS>, tower_p8_kernel<KS>)
     float* split_parts[2] = {nullptr, nullptr};
     static constexpr int kSplitMaxG = 10;
+    // "-wsplit": the image sets of block_x3w_split_kernel (two alternate), the set the last launch wrote and its images per board (0: the
+    // float stream in `cur` is current)
+    float* wsplit_parts[2] = {nullptr, nullptr};
+    int wsplit_set = 0, wsplit_g = 0;
 
     Builder(RiseNet& n, const NetFile& file) : net(n), im(*n.impl_), nf(file), prec(n.prec_), dev(n.dev_) {}
     void read_model();
@@ -86,6 +92,7 @@ template <typename T> struct RiseNet::Builder {
     void transformer_block_x3w(const NtbFold& n);
     void flush_tower();
     void flush_x3_run();
+    void wsplit_finish();
     void one_launch_head();
     void policy_head();
     void softmax();
@@ -200,7 +207,9 @@ template <typename T> BlockPlan RiseNet::Builder<T>::plan(size_t i) const {
         return {Family::Transformer, false};
     }
     // "-wblock": every other block of a 128 / 192 / 224-channel net, also between transformer blocks; the gate comes from the launches in front
-    if (prec.wblock && prec.x3() && !dense_blocks && block_x3w_supports(C, k)) return {Family::WBlock, false};
+    // "-wsplit": the same blocks over several workgroups per board in a net made for few boards (a larger net builds "-wnet"'s list)
+    if (prec.wblock && prec.x3() && !dense_blocks && block_x3w_supports(C, k))
+        return {prec.wsplit && B <= kBoardSplitMaxBatch ? Family::WSplit : Family::WBlock, false};
     if (tower_ok) return {Family::Tower, i > 0};          // 3x3 and 5x5 blocks in one run; the run's first gate comes from an SE launch
     if (x3_tower) {
         // the 5x5 blocks (RISEv3.3) run in tower launches of their own (tower_*_kernel<5>); small batches run 3x3 blocks split-board (float16x3
@@ -285,6 +294,7 @@ template <typename T> void RiseNet::Builder<T>::add_se(Op op, bool consumer_fuse
             se_gate = static_cast<float*>(im.dalloc(size_t(B) * C * sizeof(float)));
         }
         if (im.ops[prod_op].kind == OpKind::Tower) im.ops[prod_op].tw.pool_out = se_pool;
+        else if (im.ops[prod_op].kind == OpKind::X3WSplitFinish) im.ops[prod_op].ws.blk.pool_out = se_pool;
         else im.ops[prod_op].blk.pool_out = se_pool;
         op.kind = OpKind::SEGate;
         op.x = se_pool;
@@ -400,6 +410,7 @@ template <typename T> void RiseNet::Builder<T>::bottleneck_blocks() {
         const std::string p = "body_spatial." + std::to_string(i + 1);
         const int cop = cops[i], k = ks[i];
         const BlockPlan bp = plan(i);
+        if (bp.family != Family::WSplit) wsplit_finish();        // whatever else runs here reads the float stream
         if (bp.family == Family::Transformer || bp.family == Family::WNtb) {
             if (bp.family == Family::WNtb) transformer_block_x3w(fold_ntb(nf, p, C));
             else transformer_block(i);
@@ -423,7 +434,10 @@ template <typename T> void RiseNet::Builder<T>::bottleneck_blocks() {
             if (se.kind == 1) xb.se_w2t = im.upload(pk.second);
             else xb.se_b = im.upload(se.b);
         } else if (se.kind) {
-            add_se(se_op(se), bp.family == Family::Fused || bp.family == Family::WBlock);
+            // (a gated split-board block reads the float stream: the finish launch in front of it leaves the stream's channel sums as the
+            // one-launch block before it would have, its gate is WBlock's; behind the stem or a transformer block: the in-place SE launch)
+            if (bp.family == Family::WSplit) wsplit_finish();
+            add_se(se_op(se), bp.family == Family::Fused || bp.family == Family::WBlock || bp.family == Family::WSplit);
         }
         macs += se.macs;
         if (bp.family == Family::Tower) {
@@ -512,6 +526,44 @@ template <typename T> void RiseNet::Builder<T>::bottleneck_blocks() {
             im.ops.push_back(op);
             ++wblock_ops;
             std::swap(cur, nxt);
+        } else if (bp.family == Family::WSplit) {
+            // block_x3w_split_kernel: WBlock's images; the block reads the images of the launch before it (or the float stream: the first
+            // block, behind a transformer block, a gated block) and writes the other image set.  G and gin are those of a whole batch;
+            // a call of fewer boards takes its own (launch_op).
+            const int cop_pad = round_up(cop, 64);
+            const X3BlockPack pk = pack_x3_block(fold_block(nf, p), C, cop, k, cop_pad, false);
+            if (!wsplit_parts[0]) {
+                int max_chunks = 1;
+                for (size_t q = 0; q < cops.size(); ++q)
+                    if (!ntb[q]) max_chunks = std::max(max_chunks, x3w_split_chunks(round_up(cops[q], 64)));
+                const size_t images = size_t(std::min(max_chunks, int(kX3WSplitMaxG)));       // G <= that, and a call has at most B boards
+                for (auto& q : wsplit_parts) q = static_cast<float*>(im.dalloc(size_t(B) * images * kSquares * C * sizeof(float)));
+            }
+            Op op;
+            op.kind = OpKind::BlockX3WSplit;
+            BlockArgs& ba = op.ws.blk;
+            ba.w1pk = im.upload(pk.w1.hi);
+            ba.w1pk_lo = im.upload(pk.w1.lo);
+            ba.w3pk = im.upload(pk.w3.hi);
+            ba.w3pk_lo = im.upload(pk.w3.lo);
+            ba.dwpk = im.upload(pk.dw);
+            ba.b3 = im.upload(pk.b3);
+            ba.batch = B;
+            ba.C = C;
+            ba.cop_pad = cop_pad;
+            ba.ks = k;
+            ba.gate = pending_gate;
+            pending_gate = nullptr;
+            op.ws.stream_in = wsplit_g == 0 ? 1 : 0;
+            op.ws.x_parts = wsplit_g == 0 ? reinterpret_cast<const float*>(cur) : wsplit_parts[wsplit_set];
+            op.ws.gin = std::max(1, wsplit_g);
+            wsplit_set ^= 1;
+            op.ws.y_parts = wsplit_parts[wsplit_set];
+            op.ws.G = x3w_split_shares(cop_pad, B, net.cu_count_);
+            wsplit_g = op.ws.G;
+            prod_op = -1;                  // (channel sums come from the finish launch, wsplit_finish)
+            im.ops.push_back(op);
+            ++wblock_ops;
         } else {
             add_conv(p + ".body.0", p + ".body.1", cur, e, nullptr, C, C, cop, 1, true, nullptr);   // 1x1 expand + BN + ReLU
             {   // depthwise k x k + BN + ReLU
@@ -536,6 +588,23 @@ template <typename T> void RiseNet::Builder<T>::bottleneck_blocks() {
     }
     flush_tower();
     flush_x3_run();
+    wsplit_finish();
+}
+
+// "-wsplit": the images of the last split-board block -> the float stream `cur`, in front of whatever reads the stream.  It can emit the
+// stream's channel sums (add_se) as a one-launch block does.
+template <typename T> void RiseNet::Builder<T>::wsplit_finish() {
+    if (wsplit_g == 0) return;
+    Op fin;
+    fin.kind = OpKind::X3WSplitFinish;
+    fin.ws.x_parts = wsplit_parts[wsplit_set];
+    fin.ws.gin = wsplit_g;
+    fin.ws.blk.y = cur;
+    fin.ws.blk.C = C;
+    fin.ws.blk.batch = B;
+    prod_op = int(im.ops.size());
+    im.ops.push_back(fin);
+    wsplit_g = 0;
 }
 
 // NTB (next_vit_official_modules.py:267-335) on the layer kernels.  The block's C-wide tile xs (= nxt) holds the E_MHSA part in channels
@@ -963,6 +1032,7 @@ template <typename T> void RiseNet::build(const NetFile& nf) {
     init_block_kernel_attributes<T>();
     init_x3_kernel_attributes();
     init_x3_wblock_kernel_attributes();
+    init_x3_wsplit_kernel_attributes();
     init_x3_wntb_kernel_attributes();
     init_tower_kernel_attributes();
     init_restower_kernel_attributes();

@@ -54,7 +54,11 @@ typedef struct mi_net mi_net;
  * order.  Refused on every other precision and on a net none of whose blocks qualifies (256 channels, dense block families, other widths).
  * Suffix "-wnet" ("float16x3-wnet", "float16p8-wnet"): everything "-wblock" means, and every NextViT transformer block of such a net
  * (C = 128 / 192 / 224 with E_MHSA widths 96 / 160 / 160 and an Mlp of 2 C) runs in one launch instead of nine, the same bits as the nine
- * (DESIGN 9a); a transformer block of another shape keeps its launches.  Opt-in; refused like "-wblock", and by expert sets. */
+ * (DESIGN 9a); a transformer block of another shape keeps its launches.  Opt-in; refused like "-wblock", and by expert sets.
+ * Suffix "-wsplit" ("float16x3-wsplit", "float16p8-wsplit"): everything "-wnet" means, and a net made for at most 64 boards runs each of
+ * "-wblock"'s blocks over several workgroups per board (the split-board forward of the 256-channel nets at AlphaVile's
+ * widths), within 2e-5 of "-wnet" on logits and value; a net made for more boards is a "-wnet" net whose few-board calls go to such a
+ * companion net.  Opt-in; refused like "-wnet", with "-unfused" and with "-1wg". */
 mi_net* mi_net_create(const char* model_dir, int device_id, int batch_size, const char* precision);
 /* Precision "int8" -- the reference's calibrated INT8 mode (TensorRT INT8 with an Int8EntropyCalibrator2 over the engine's
  * ChessBatchStream positions, engine/src/nn/tensorrtapi.cpp:334-360, environments/chess_related/chessbatchstream.cpp:44-94) -- needs one
