@@ -108,7 +108,7 @@ ExpertSet::ExpertSet(const std::string& model_dir, int device_id, int batch_size
     : BoardNet(device_id) {
     if (batch_size <= 0) throw std::invalid_argument("batch size must be positive");
     const Precision prec = parse_precision(precision);
-    // (every kernel-family suffix too: "-1wg", "-3k", "-8w", "-1b" / "-2b", "-unfused", "-perblock", "-wblock", "-wnet", "-wsplit" are variants no routed call was checked in)
+    // (every kernel-family suffix too: "-1wg", "-3k", "-8w", "-1b" / "-2b", "-unfused", "-perblock", "-wblock", "-wnet", "-wsplit", "-wtower" are variants no routed call was checked in)
     if (prec.mode != Precision::Mode::Float16x3 || !prec.fused || !prec.tower || !prec.one_launch || prec.thin_waves || !prec.board_split || prec.boards_per_wg != 0 ||
         prec.wblock || prec.wnet)
         throw std::invalid_argument("an expert set runs Precision float16x3 (got '" + precision + "'): the routed forward is checked bit for bit in that mode only");

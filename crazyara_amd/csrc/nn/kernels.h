@@ -158,6 +158,29 @@ int x3w_split_shares(int cop_pad, int boards, int cu_count);     // G of a call:
 void launch_block_x3w_split(const X3WSplitArgs& a, hipStream_t s);
 void launch_x3w_split_finish(const float* parts, int gin, float* y, float* pool_out, int batch, int C, hipStream_t s);
 void init_x3_wsplit_kernel_attributes();
+// Kernel family "-wtower" (x3_wtower.cpp: tower_x3w_kernel<C>): a run of two or more consecutive blocks of "-wblock" in one launch, one
+// workgroup per board, the bits of one launch_block_x3w per block.  The board is staged and split once; every block's output stays in the
+// lanes' registers in f32 and, split, in the operand tiles; 3x3 and 5x5 blocks mix in a run.  Only the first block may be gated (`gate`, as
+// BlockArgs::gate); the last block stores the stream and, with pool_out, its channel sums (BlockArgs::pool_out).  x and y differ.
+struct X3WTowerBlock {
+    const void *w1pk, *w1pk_lo, *w3pk, *w3pk_lo;     // as launch_block_x3w takes them (pack.cpp: pack_x3_block, cop_pad a multiple of 64)
+    const float* dwpk;                               // the 3x3 or the 5x5 records of the block (pack_x3_depthwise_records)
+    const float* b3;                                 // [C]
+    int cop_pad, ks;
+};
+static_assert(sizeof(X3WTowerBlock) == 56, "tower_x3w_kernel indexes a device array of these");
+struct X3WTowerArgs {
+    const float* x;                  // [B][64][C]
+    float* y;                        // [B][64][C]
+    const X3WTowerBlock* blocks;     // device array
+    int nblocks;
+    const float* gate;               // optional [B][C]: the first block's SE gate
+    float* pool_out;                 // optional [B][C]: the channel sums of the last block's output
+    int batch, C;
+};
+bool tower_x3w_supports(int C, int ks);
+void launch_tower_x3w(const X3WTowerArgs& a, hipStream_t s);
+void init_x3_wtower_kernel_attributes();
 // Kernel family "-wnet" (x3_wntb.cpp: ntb_x3w_kernel<C>): a NextViT transformer block of a 128 / 192 / 224-channel net in one launch, float16x3
 // arithmetic, the bits of the nine layer launches (RiseNet::Builder::transformer_block).  Every layer's weights are the hi / lo fragment
 // images of pack_dense_split (pack.cpp: pack_x3_ntb; the grouped 3x3 as [cout tile][tap] fragments of its 32-channel groups) and its

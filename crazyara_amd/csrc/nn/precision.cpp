@@ -48,7 +48,8 @@ Precision parse_precision(const std::string& precision) {
     if (strip("-1wg")) v.board_split = false;
     if (strip("-1b")) v.boards_per_wg = 1;
     else if (strip("-2b")) v.boards_per_wg = 2;
-    if (strip("-wsplit")) v.wsplit = v.wnet = v.wblock = true;   // "-wnet", and split-board blocks in nets made for few boards (x3_wsplit.cpp)
+    if (strip("-wtower")) v.wtower = v.wnet = v.wblock = true;   // "-wnet", and runs of consecutive blocks in one launch (x3_wtower.cpp)
+    else if (strip("-wsplit")) v.wsplit = v.wnet = v.wblock = true;   // "-wnet", and split-board blocks in nets made for few boards (x3_wsplit.cpp)
     else if (strip("-wnet")) v.wnet = v.wblock = true;   // "-wblock" plus the transformer blocks in one launch each (x3_wntb.cpp)
     else if (strip("-wblock")) v.wblock = true;    // one-launch blocks at trunk widths 128 / 192 / 224 (x3_wblock.cpp); which blocks qualify is the builder's business
     if (strip("-unfused")) v.fused = v.tower = false;
@@ -72,6 +73,8 @@ Precision parse_precision(const std::string& precision) {
     for (const auto& m : kModes)
         if (prec == m.first) {
             v.mode = m.second;
+            if (v.wtower && !v.x3()) throw std::invalid_argument("`-wtower` is a float16x3 kernel family (float16x3-wtower | float16p8-wtower), got '" + precision + "'");
+            if (v.wtower && !v.fused) throw std::invalid_argument("`-wtower` and `-unfused` exclude each other, got '" + precision + "'");
             if (v.wsplit && !v.x3()) throw std::invalid_argument("`-wsplit` is a float16x3 kernel family (float16x3-wsplit | float16p8-wsplit), got '" + precision + "'");
             if (v.wsplit && !v.fused) throw std::invalid_argument("`-wsplit` and `-unfused` exclude each other, got '" + precision + "'");
             if (v.wsplit && !v.board_split)

@@ -35,6 +35,8 @@ struct Precision {
                                // ntb_x3w_kernel) instead of nine; opt-in
     bool wsplit = false;       // "-wsplit": "-wnet" (implied) and, in a net made for at most kBoardSplitMaxBatch boards, every block of "-wblock" over
                                // several workgroups per board (x3_wsplit.cpp: block_x3w_split_kernel); opt-in
+    bool wtower = false;       // "-wtower": "-wnet" (implied) and every maximal run of two or more consecutive blocks of "-wblock" in one launch
+                               // (x3_wtower.cpp: tower_x3w_kernel), a gated block starting a run; opt-in
     int boards_per_wg = 0;     // dense residual tower: 0 = by batch size (2 from 512 boards), 1 / 2 = forced ("-1b" / "-2b")
     bool fp16() const { return mode == Mode::Float16 || mode == Mode::Fp8 || mode == Mode::Int8; }   // f16 activations (else float)
     bool x3() const { return mode == Mode::Float16x3 || mode == Mode::Float16p8; }    // split-operand f16 MFMAs (x3.hip)
@@ -57,7 +59,7 @@ public:
     //            (both kept for A/B measurements and as independent implementations in the parity tests); "-wblock" on float16x3 /
     //            float16p8 runs the mobile-bottleneck blocks of a 128 / 192 / 224-channel net (AlphaVile) one launch each, "-wnet" its
     //            transformer blocks too, "-wsplit" is "-wnet" with those blocks over several workgroups per board in a net made for at
-    //            most kBoardSplitMaxBatch boards.   Throws std::invalid_argument / std::runtime_error.
+    //            most kBoardSplitMaxBatch boards, "-wtower" is "-wnet" with every run of consecutive such blocks in one launch.   Throws std::invalid_argument / std::runtime_error.
     RiseNet(const std::string& model_path, int device_id, int batch_size, const std::string& precision) : RiseNet(model_path, device_id, batch_size, precision, nullptr) {}
     ~RiseNet() override;
 

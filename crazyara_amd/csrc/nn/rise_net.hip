@@ -158,6 +158,12 @@ template <typename T> void RiseNet::launch_op(int i, hipStream_t s, ForwardCall&
             launch_block_x3w(a, s);
             break;
         }
+        case OpKind::TowerX3W: {
+            X3WTowerArgs a = op.wt;
+            a.batch = B;
+            launch_tower_x3w(a, s);
+            break;
+        }
         case OpKind::BlockX3WSplit: {                              // the shares per board follow the boards of THIS forward; a launch reads as
             X3WSplitArgs a = op.ws;                                // many images per board as the launch before it wrote
             if (n > 0) {
@@ -275,6 +281,7 @@ const char* RiseNet::op_name(int i) const {
         case OpKind::Attention: return "attention";
         case OpKind::BlockX3W: return "block_x3w";
         case OpKind::NtbX3W: return "ntb_x3w";
+        case OpKind::TowerX3W: return "tower_x3w";
         case OpKind::BlockX3WSplit: return "block_x3w_split";
         case OpKind::X3WSplitFinish: return "x3w_split_finish";
     }

@@ -21,6 +21,8 @@ enum class Family {
     WBlock,    // float16x3 / float16p8 with "-wblock" at 128 / 192 / 224 channels: one launch per block (x3_wblock.cpp: block_x3w_kernel)
     WSplit,    // float16x3 / float16p8 with "-wsplit" in a net made for few boards: WBlock's blocks over several workgroups per board
                // (x3_wsplit.cpp: block_x3w_split_kernel)
+    WTower,    // float16x3 / float16p8 with "-wtower": WBlock's blocks, every maximal run of two or more consecutive ones in one launch
+               // (x3_wtower.cpp: tower_x3w_kernel); a gated block starts a run, a run of one is a WBlock launch
     Layers,    // expand, depthwise and project as three layer launches
     Transformer,  // a NextViT transformer block: conv GEMMs and the attention kernel (Builder::transformer_block)
     WNtb       // float16x3 / float16p8 with "-wnet": a transformer block of rise_config.ntb_widths in one launch (x3_wntb.cpp: ntb_x3w_kernel)
@@ -72,6 +74,8 @@ template <typename T> struct RiseNet::Builder {
     // float stream in `cur` is current)
     float* wsplit_parts[2] = {nullptr, nullptr};
     int wsplit_set = 0, wsplit_g = 0;
+    // "-wtower": the blocks of the open run as launch_block_x3w would take them (x, y and batch are the flush's); the first one's gate is the run's
+    std::vector<BlockArgs> wrun;
 
     Builder(RiseNet& n, const NetFile& file) : net(n), im(*n.impl_), nf(file), prec(n.prec_), dev(n.dev_) {}
     void read_model();
@@ -93,6 +97,7 @@ template <typename T> struct RiseNet::Builder {
     void flush_tower();
     void flush_x3_run();
     void wsplit_finish();
+    void flush_wrun();
     void one_launch_head();
     void policy_head();
     void softmax();
@@ -208,8 +213,9 @@ template <typename T> BlockPlan RiseNet::Builder<T>::plan(size_t i) const {
     }
     // "-wblock": every other block of a 128 / 192 / 224-channel net, also between transformer blocks; the gate comes from the launches in front
     // "-wsplit": the same blocks over several workgroups per board in a net made for few boards (a larger net builds "-wnet"'s list)
+    // "-wtower": the same blocks, consecutive ones in one launch (bottleneck_blocks, flush_wrun), whatever the batch the net is made for
     if (prec.wblock && prec.x3() && !dense_blocks && block_x3w_supports(C, k))
-        return {prec.wsplit && B <= kBoardSplitMaxBatch ? Family::WSplit : Family::WBlock, false};
+        return {prec.wtower ? Family::WTower : prec.wsplit && B <= kBoardSplitMaxBatch ? Family::WSplit : Family::WBlock, false};
     if (tower_ok) return {Family::Tower, i > 0};          // 3x3 and 5x5 blocks in one run; the run's first gate comes from an SE launch
     if (x3_tower) {
         // the 5x5 blocks (RISEv3.3) run in tower launches of their own (tower_*_kernel<5>); small batches run 3x3 blocks split-board (float16x3
@@ -294,6 +300,7 @@ template <typename T> void RiseNet::Builder<T>::add_se(Op op, bool consumer_fuse
             se_gate = static_cast<float*>(im.dalloc(size_t(B) * C * sizeof(float)));
         }
         if (im.ops[prod_op].kind == OpKind::Tower) im.ops[prod_op].tw.pool_out = se_pool;
+        else if (im.ops[prod_op].kind == OpKind::TowerX3W) im.ops[prod_op].wt.pool_out = se_pool;
         else if (im.ops[prod_op].kind == OpKind::X3WSplitFinish) im.ops[prod_op].ws.blk.pool_out = se_pool;
         else im.ops[prod_op].blk.pool_out = se_pool;
         op.kind = OpKind::SEGate;
@@ -411,6 +418,7 @@ template <typename T> void RiseNet::Builder<T>::bottleneck_blocks() {
         const int cop = cops[i], k = ks[i];
         const BlockPlan bp = plan(i);
         if (bp.family != Family::WSplit) wsplit_finish();        // whatever else runs here reads the float stream
+        if (bp.family != Family::WTower) flush_wrun();           // a transformer block or any other family ends a run
         if (bp.family == Family::Transformer || bp.family == Family::WNtb) {
             if (bp.family == Family::WNtb) transformer_block_x3w(fold_ntb(nf, p, C));
             else transformer_block(i);
@@ -437,7 +445,9 @@ template <typename T> void RiseNet::Builder<T>::bottleneck_blocks() {
             // (a gated split-board block reads the float stream: the finish launch in front of it leaves the stream's channel sums as the
             // one-launch block before it would have, its gate is WBlock's; behind the stem or a transformer block: the in-place SE launch)
             if (bp.family == Family::WSplit) wsplit_finish();
-            add_se(se_op(se), bp.family == Family::Fused || bp.family == Family::WBlock || bp.family == Family::WSplit);
+            // (only a run's first block may be gated: the run in front of a gated block ends here, its last block leaves the channel sums)
+            if (bp.family == Family::WTower) flush_wrun();
+            add_se(se_op(se), bp.family == Family::Fused || bp.family == Family::WBlock || bp.family == Family::WSplit || bp.family == Family::WTower);
         }
         macs += se.macs;
         if (bp.family == Family::Tower) {
@@ -526,6 +536,25 @@ template <typename T> void RiseNet::Builder<T>::bottleneck_blocks() {
             im.ops.push_back(op);
             ++wblock_ops;
             std::swap(cur, nxt);
+        } else if (bp.family == Family::WTower) {
+            // WBlock's images and arguments; the launch is flush_wrun's
+            const int cop_pad = round_up(cop, 64);
+            const X3BlockPack pk = pack_x3_block(fold_block(nf, p), C, cop, k, cop_pad, false);
+            BlockArgs ba{};
+            ba.w1pk = im.upload(pk.w1.hi);
+            ba.w1pk_lo = im.upload(pk.w1.lo);
+            ba.w3pk = im.upload(pk.w3.hi);
+            ba.w3pk_lo = im.upload(pk.w3.lo);
+            ba.dwpk = im.upload(pk.dw);
+            ba.b3 = im.upload(pk.b3);
+            ba.batch = B;
+            ba.C = C;
+            ba.cop_pad = cop_pad;
+            ba.ks = k;
+            ba.gate = pending_gate;            // (set for an empty run only: a gated block has just ended the run in front of it)
+            pending_gate = nullptr;
+            wrun.push_back(ba);
+            ++wblock_ops;
         } else if (bp.family == Family::WSplit) {
             // block_x3w_split_kernel: WBlock's images; the block reads the images of the launch before it (or the float stream: the first
             // block, behind a transformer block, a gated block) and writes the other image set.  G and gin are those of a whole batch;
@@ -589,6 +618,38 @@ template <typename T> void RiseNet::Builder<T>::bottleneck_blocks() {
     flush_tower();
     flush_x3_run();
     wsplit_finish();
+    flush_wrun();
+}
+
+// "-wtower": the open run cur -> nxt.  One block: "-wblock"'s launch, unchanged; two or more: one tower_x3w_kernel launch over a device array of
+// the blocks' records (an upload of the net's, freed with it).  Either can emit the stream's channel sums (add_se).
+template <typename T> void RiseNet::Builder<T>::flush_wrun() {
+    if (wrun.empty()) return;
+    Op op;
+    if (wrun.size() == 1) {
+        op.kind = OpKind::BlockX3W;
+        op.blk = wrun[0];
+        op.blk.x = cur;
+        op.blk.y = nxt;
+    } else {
+        std::vector<X3WTowerBlock> recs;
+        for (const BlockArgs& ba : wrun) {
+            if (ba.gate && &ba != &wrun[0]) throw std::logic_error("flush_wrun: a gated block inside a run");
+            recs.push_back(X3WTowerBlock{ba.w1pk, ba.w1pk_lo, ba.w3pk, ba.w3pk_lo, ba.dwpk, ba.b3, ba.cop_pad, ba.ks});
+        }
+        op.kind = OpKind::TowerX3W;
+        op.wt.x = reinterpret_cast<const float*>(cur);
+        op.wt.y = reinterpret_cast<float*>(nxt);
+        op.wt.blocks = im.upload(recs);
+        op.wt.nblocks = int(recs.size());
+        op.wt.gate = wrun[0].gate;
+        op.wt.batch = B;
+        op.wt.C = C;
+    }
+    prod_op = int(im.ops.size());
+    im.ops.push_back(op);
+    wrun.clear();
+    std::swap(cur, nxt);
 }
 
 // "-wsplit": the images of the last split-board block -> the float stream `cur`, in front of whatever reads the stream.  It can emit the
@@ -1014,7 +1075,7 @@ template <typename T> void RiseNet::build(const NetFile& nf) {
     else if (b.dense_blocks) b.dense_layer_blocks();
     else b.bottleneck_blocks();
     if (prec_.wnet && b.wblock_ops == 0 && b.wntb_ops == 0)
-        throw std::runtime_error("`-wnet` runs the mobile-bottleneck and transformer blocks of 128 / 192 / 224-channel nets in one launch each: no block of this model qualifies (" +
+        throw std::runtime_error(std::string(prec_.wtower ? "`-wtower`" : "`-wnet`") + " runs the mobile-bottleneck and transformer blocks of 128 / 192 / 224-channel nets in one launch each: no block of this model qualifies (" +
                                  std::to_string(b.C) + " channels, " + (b.dense_blocks ? "dense residual blocks" : "mobile-bottleneck blocks") +
                                  "); use the precision without the suffix");
     if (prec_.wblock && !prec_.wnet && b.wblock_ops == 0)
@@ -1033,6 +1094,7 @@ template <typename T> void RiseNet::build(const NetFile& nf) {
     init_x3_kernel_attributes();
     init_x3_wblock_kernel_attributes();
     init_x3_wsplit_kernel_attributes();
+    init_x3_wtower_kernel_attributes();
     init_x3_wntb_kernel_attributes();
     init_tower_kernel_attributes();
     init_restower_kernel_attributes();

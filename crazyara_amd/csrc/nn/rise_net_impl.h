@@ -18,7 +18,7 @@ namespace cra {
             throw std::runtime_error(std::string("HIP error ") + hipGetErrorString(_e) + " at " #expr);      \
     } while (0)
 
-enum class OpKind { PlanesToAct, Conv, Depthwise, SE, ValueHead, Softmax, Block, ValueFinal, SEGate, Tower, Head, Stem, ResTower, Forward, TowerX3, BlockX3Split, X3SplitFinish, HeadsSmall, Attention, BlockX3W, NtbX3W, BlockX3WSplit, X3WSplitFinish };
+enum class OpKind { PlanesToAct, Conv, Depthwise, SE, ValueHead, Softmax, Block, ValueFinal, SEGate, Tower, Head, Stem, ResTower, Forward, TowerX3, BlockX3Split, X3SplitFinish, HeadsSmall, Attention, BlockX3W, NtbX3W, BlockX3WSplit, X3WSplitFinish, TowerX3W };
 
 struct Op {
     OpKind kind;
@@ -41,6 +41,7 @@ struct Op {
     X3TowerArgs tx{};
     X3SplitArgs xs{};             // BlockX3Split; X3SplitFinish: x_parts, gin, batch and (xs_y) the float stream
     float* xs_y = nullptr;
+    X3WTowerArgs wt{};            // TowerX3W (x3_wtower.cpp); wt.blocks is an upload of the net's (Impl::upload), freed with it
     X3WSplitArgs ws{};            // BlockX3WSplit (x3_wsplit.cpp); X3WSplitFinish: x_parts, gin, blk.C and the float stream blk.y, blk.pool_out
 };
 

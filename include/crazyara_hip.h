@@ -58,7 +58,11 @@ typedef struct mi_net mi_net;
  * Suffix "-wsplit" ("float16x3-wsplit", "float16p8-wsplit"): everything "-wnet" means, and a net made for at most 64 boards runs each of
  * "-wblock"'s blocks over several workgroups per board (the split-board forward of the 256-channel nets at AlphaVile's
  * widths), within 2e-5 of "-wnet" on logits and value; a net made for more boards is a "-wnet" net whose few-board calls go to such a
- * companion net.  Opt-in; refused like "-wnet", with "-unfused" and with "-1wg". */
+ * companion net.  Opt-in; refused like "-wnet", with "-unfused" and with "-1wg".
+ * Suffix "-wtower" ("float16x3-wtower", "float16p8-wtower"): everything "-wnet" means, and every maximal run of two or more consecutive
+ * blocks of "-wblock" runs in one launch, 3x3 and 5x5 blocks alike, the same bits as "-wnet"; a gated block starts a run, a
+ * transformer block ends one, a lone block keeps "-wblock"'s launch.  Opt-in; refused like "-wnet" and with "-unfused"; one of
+ * "-wblock" / "-wnet" / "-wsplit" / "-wtower" at a time. */
 mi_net* mi_net_create(const char* model_dir, int device_id, int batch_size, const char* precision);
 /* Precision "int8" -- the reference's calibrated INT8 mode (TensorRT INT8 with an Int8EntropyCalibrator2 over the engine's
  * ChessBatchStream positions, engine/src/nn/tensorrtapi.cpp:334-360, environments/chess_related/chessbatchstream.cpp:44-94) -- needs one
