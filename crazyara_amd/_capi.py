@@ -40,6 +40,7 @@ SIGNATURES = {
     "mi_net_time_forward": (C.c_int, [C.c_void_p, C.c_int, c_float_p]),
     "mi_net_op_count": (C.c_int, [C.c_void_p]),
     "mi_net_time_ops": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), c_float_p]),
+    "mi_net_op_kernel": (C.c_char_p, [C.c_void_p, C.c_int]),
     "mi_net_submit_boards": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi_net_submit_boards_gathered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]),

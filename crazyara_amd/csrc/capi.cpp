@@ -231,6 +231,12 @@ int mi_net_time_forward(mi_net* net, int iters, float* ms_total) {
     return guard([&] { *ms_total = plain_net(net, "a device-resident forward").time_forward(iters); });
 }
 int mi_net_op_count(const mi_net* net) { return net && net->plain ? net->plain->launches_per_forward() : 0; }
+const char* mi_net_op_kernel(const mi_net* net, int op) {
+    if (!net || !net->plain || op < 0 || op >= net->plain->launches_per_forward()) { g_err = "mi_net_op_kernel: no such op"; return nullptr; }
+    const char* name = nullptr;
+    if (guard([&] { name = net->plain->op_kernel(op); })) return nullptr;
+    return name;
+}
 int mi_net_time_ops(mi_net* net, int iters, const char** names, float* ms) {
     if (!net || !ms) { g_err = "null argument"; return 1; }
     return guard([&] {

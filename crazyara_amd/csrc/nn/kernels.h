@@ -125,11 +125,17 @@ struct X3TowerArgs {
     int symmetric;        // development (CRA_X3_TOWER=symmetric when the net was made): float16x3's 3x3 runs on tower_x3_kernel, every wave all three phases
     int no_tail;          // CRA_X3_NO_TAIL when the net was made: float16x3's two-role runs on tower_x3_roles_kernel (every chunk 128 channels), the
                           // bit-for-bit reference of tower_x3_tail_kernel
+    int no_quad;          // CRA_X3_NO_QUAD when the net was made: float16x3's 3x3 runs stay on tower_x3_tail_kernel, the reference of
+                          // tower_x3_quad_kernel (x3_quad.cpp: transposed expand accumulators, the quadrant depthwise)
 };
 void launch_tower_x3(const X3TowerArgs& a, hipStream_t s);
+const char* tower_x3_kernel_name(const X3TowerArgs& a);     // the kernel launch_tower_x3 sends these arguments to (static string; RiseNet::op_kernel)
 // float16x3's two-role tower with a 64-channel last chunk in blocks whose X3TowerBlock::tail is set (x3_tail.cpp); launch_tower_x3 calls it
 void launch_tower_x3_tail(const X3TowerArgs& a, hipStream_t s);
 void init_x3_tail_kernel_attributes();
+// the same tower with the EXPAND waves' accumulators transposed (x3_quad.cpp), 3x3 runs only; launch_tower_x3 calls it
+void launch_tower_x3_quad(const X3TowerArgs& a, hipStream_t s);
+void init_x3_quad_kernel_attributes();
 // Kernel family "-wblock" (x3_wblock.cpp: block_x3w_kernel<C, KS>): block_x3_kernel's sibling for trunk widths 128 / 192 / 224 with a 3x3 or
 // 5x5 depthwise, float16x3 arithmetic.  BlockArgs as launch_block_x3 takes them, except that cop_pad is a multiple of 64 (a last chunk of
 // 64 channels runs as such) and dwpk holds the 3x3 or the 5x5 records (pack.cpp: pack_x3_depthwise_records).  launch_se_gate_w: the SE gate

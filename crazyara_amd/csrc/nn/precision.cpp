@@ -32,6 +32,7 @@ RiseNet::DevSwitches::DevSwitches() {
     if (const char* e = getenv("CRA_VALUE_HEAD_VARIANT")) value_head_variant = atoi(e);
     x3_no_head_chain = getenv("CRA_X3_NO_HEAD_CHAIN") != nullptr;
     x3_no_tail = getenv("CRA_X3_NO_TAIL") != nullptr;
+    x3_no_quad = getenv("CRA_X3_NO_QUAD") != nullptr;
     small_batch_heads_apart = getenv("CRA_SMALL_BATCH_HEADS_APART") != nullptr;
 }
 

@@ -124,6 +124,7 @@ public:
     // per-launch bookkeeping (bench.py roofline: live hipEvent timing of each op on the net stream)
     int launches_per_forward() const { return launches_; }
     const char* op_name(int i) const;
+    const char* op_kernel(int i) const;                // the kernel op i launches where one op name covers several (tower_x3: launch_tower_x3's choice), else op_name(i)
     void time_ops(int iters, float* ms);               // ms[i] += elapsed of op i, summed over iters (un-graphed launches)
     float time_forward(int iters);                     // graph replays between two events, returns ms
 
@@ -187,6 +188,7 @@ private:
         int value_head_variant = 0;     // CRA_VALUE_HEAD_VARIANT: kernels.h: ValueHeadArgs::variant
         bool x3_no_head_chain = false;  // CRA_X3_NO_HEAD_CHAIN: the float16x3 policy head as two launches
         bool x3_no_tail = false;        // CRA_X3_NO_TAIL: the float16x3 two-role tower runs every chunk at 128 channels (tower_x3_roles_kernel)
+        bool x3_no_quad = false;        // CRA_X3_NO_QUAD: the float16x3 two-role tower's 3x3 runs stay on tower_x3_tail_kernel (not tower_x3_quad_kernel)
         bool small_batch_heads_apart = false;   // CRA_SMALL_BATCH_HEADS_APART: a small batch's policy conv and value head as two launches
         DevSwitches();
     } dev_;

@@ -288,6 +288,11 @@ const char* RiseNet::op_name(int i) const {
     return "?";
 }
 
+const char* RiseNet::op_kernel(int i) const {
+    const Op& op = impl_->ops.at(i);
+    return op.kind == OpKind::TowerX3 ? tower_x3_kernel_name(op.tx) : op_name(i);
+}
+
 void RiseNet::time_ops(int iters, float* ms) {
     HIP_CHECK(hipSetDevice(device_));
     hipEvent_t e0, e1;

@@ -823,6 +823,7 @@ template <typename T> void RiseNet::Builder<T>::flush_x3_run() {
         op.tx.ks = x3_run_ks;
         op.tx.symmetric = dev.x3_symmetric ? 1 : 0;
         op.tx.no_tail = dev.x3_no_tail ? 1 : 0;
+        op.tx.no_quad = dev.x3_no_quad ? 1 : 0;
         im.ops.push_back(op);
     }
     x3_blocks.clear();

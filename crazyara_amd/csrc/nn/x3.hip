@@ -2195,6 +2195,7 @@ void init_x3_kernel_attributes() {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tower_x3_roles_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, int(X3Block::lds_bytes));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tower_x3_roles_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, int(X3Block::lds_bytes + 8192));
     init_x3_tail_kernel_attributes();                                   // tower_x3_tail_kernel<3 | 5> (x3_tail.cpp)
+    init_x3_quad_kernel_attributes();                                   // tower_x3_quad_kernel<3> (x3_quad.cpp)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tower_p8_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, int(X3Block::lds_bytes));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tower_p8_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, int(X3Block::lds_bytes + 8192));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_x3_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(ConvX3::lds_bytes));
@@ -2217,21 +2218,51 @@ void launch_x3_split_finish(const float* parts, int gin, float* y, int batch, hi
     const int n4 = batch * 64 * X3Block::C / 4;
     hipLaunchKernelGGL(x3_split_finish_kernel, dim3(std::min(1024, (n4 + 255) / 256)), dim3(256), 0, s, parts, gin, y, batch);
 }
-void launch_tower_x3(const X3TowerArgs& a, hipStream_t s) {
-    // CRA_X3_TOWER=symmetric (read when the net is made, rise_net.h DevSwitches): every wave runs all three phases (A/B reference);
-    // default: the two-role kernel with the 64-channel tail chunk (x3_tail.cpp), CRA_X3_NO_TAIL: the two-role kernel that runs every
-    // chunk at 128 channels.  All three add up every output in the same order: same bits.
+// CRA_X3_TOWER=symmetric (read when the net is made, rise_net.h DevSwitches): every wave runs all three phases (A/B reference);
+// default: the two-role kernel with the 64-channel tail chunk (x3_tail.cpp), CRA_X3_NO_TAIL: the two-role kernel that runs every
+// chunk at 128 channels.  All three add up every output in the same order: same bits.  3x3 runs of the default go to the kernel with
+// transposed expand accumulators (x3_quad.cpp: the same sums, the expand MFMAs' operands swapped); CRA_X3_NO_QUAD keeps them on the tail kernel.
+// One choice for the launch and for the name tower_x3_kernel_name reports (mi_net_op_kernel): the two cannot drift apart.
+namespace {
+enum class X3TowerKernel { P8_5, P8_3, Quad3, Tail5, Tail3, Roles5, Roles3, Symmetric };
+X3TowerKernel pick_tower_x3(const X3TowerArgs& a) {
     const bool symmetric = a.symmetric != 0;
     if (a.p8) {
         if (symmetric) throw std::invalid_argument("Precision float16p8 runs the two-role tower only");
-        if (a.ks == 5) hipLaunchKernelGGL(tower_p8_kernel<5>, dim3(a.batch), dim3(X3Block::NTHR), X3Block::lds_bytes + 8192, s, a);    // (2 KiB of records per tile)
-        else hipLaunchKernelGGL(tower_p8_kernel<3>, dim3(a.batch), dim3(X3Block::NTHR), X3Block::lds_bytes, s, a);
-    } else if (!symmetric && !a.no_tail) {                               // default: the two-role kernel whose half-filled last chunk runs at 64 channels
-        launch_tower_x3_tail(a, s);
-    } else if (a.ks == 5) {                                              // (5x5 runs exist in the two-role form only: the A/B switch leaves them alone)
-        hipLaunchKernelGGL(tower_x3_roles_kernel<5>, dim3(a.batch), dim3(X3Block::NTHR), X3Block::lds_bytes + 8192, s, a);
-    } else if (symmetric) hipLaunchKernelGGL(tower_x3_kernel, dim3(a.batch), dim3(X3Block::NTHR), X3Block::lds_bytes, s, a);
-    else hipLaunchKernelGGL(tower_x3_roles_kernel<3>, dim3(a.batch), dim3(X3Block::NTHR), X3Block::lds_bytes, s, a);
+        return a.ks == 5 ? X3TowerKernel::P8_5 : X3TowerKernel::P8_3;
+    }
+    if (!symmetric && !a.no_tail) {                                      // default: the two-role kernel whose half-filled last chunk runs at 64 channels
+        if (a.ks == 5) return X3TowerKernel::Tail5;
+        return a.no_quad ? X3TowerKernel::Tail3 : X3TowerKernel::Quad3;
+    }
+    if (a.ks == 5) return X3TowerKernel::Roles5;                         // (5x5 runs exist in the two-role form only: the A/B switch leaves them alone)
+    return symmetric ? X3TowerKernel::Symmetric : X3TowerKernel::Roles3;
+}
+}  // namespace
+const char* tower_x3_kernel_name(const X3TowerArgs& a) {
+    switch (pick_tower_x3(a)) {
+        case X3TowerKernel::P8_5: return "tower_p8_kernel<5>";
+        case X3TowerKernel::P8_3: return "tower_p8_kernel<3>";
+        case X3TowerKernel::Quad3: return "tower_x3_quad_kernel<3>";
+        case X3TowerKernel::Tail5: return "tower_x3_tail_kernel<5>";
+        case X3TowerKernel::Tail3: return "tower_x3_tail_kernel<3>";
+        case X3TowerKernel::Roles5: return "tower_x3_roles_kernel<5>";
+        case X3TowerKernel::Roles3: return "tower_x3_roles_kernel<3>";
+        case X3TowerKernel::Symmetric: return "tower_x3_kernel";
+    }
+    return "?";
+}
+void launch_tower_x3(const X3TowerArgs& a, hipStream_t s) {
+    switch (pick_tower_x3(a)) {
+        case X3TowerKernel::P8_5: hipLaunchKernelGGL(tower_p8_kernel<5>, dim3(a.batch), dim3(X3Block::NTHR), X3Block::lds_bytes + 8192, s, a); break;    // (2 KiB of records per tile)
+        case X3TowerKernel::P8_3: hipLaunchKernelGGL(tower_p8_kernel<3>, dim3(a.batch), dim3(X3Block::NTHR), X3Block::lds_bytes, s, a); break;
+        case X3TowerKernel::Quad3: launch_tower_x3_quad(a, s); break;
+        case X3TowerKernel::Tail5:
+        case X3TowerKernel::Tail3: launch_tower_x3_tail(a, s); break;
+        case X3TowerKernel::Roles5: hipLaunchKernelGGL(tower_x3_roles_kernel<5>, dim3(a.batch), dim3(X3Block::NTHR), X3Block::lds_bytes + 8192, s, a); break;
+        case X3TowerKernel::Roles3: hipLaunchKernelGGL(tower_x3_roles_kernel<3>, dim3(a.batch), dim3(X3Block::NTHR), X3Block::lds_bytes, s, a); break;
+        case X3TowerKernel::Symmetric: hipLaunchKernelGGL(tower_x3_kernel, dim3(a.batch), dim3(X3Block::NTHR), X3Block::lds_bytes, s, a); break;
+    }
 }
 
 }  // namespace cra

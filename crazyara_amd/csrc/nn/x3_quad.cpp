@@ -1,41 +1,47 @@
-// Precision float16x3: the two-role tower (x3.hip: tower_x3_roles_kernel) with the last chunk of a block at 64 channels.
+// Precision float16x3: the two-role tower with a 64-channel tail chunk (x3_tail.cpp: tower_x3_tail_kernel) with the EXPAND waves'
+// accumulators TRANSPOSED -- the quadrant depthwise.
 //
-// The tower kernels run a block's expanded channels in chunks of 128 and the packers pad C_op up to a whole chunk.  RISEv2's C_op grows by
-// 64 per block, so every other block ends in a chunk whose upper 64 channels are zeros, and tower_x3_roles_kernel still pays that chunk's
-// whole expand, depthwise and project.  tower_x3_tail_kernel is the same kernel -- EXPAND waves 0-3, PROJECT waves 4-7, the same barriers
-// in the same order, the residual stream in the PROJECT waves' registers, the gate phases, the early request of the first window -- except
-// that in a block whose X3TowerBlock::tail is set the last chunk n - 1 is a 64-channel chunk:
-//   E(n - 1): an EXPAND wave expands ONE 16-channel tile, (n - 1) * 8 + w (half the MFMAs per k-slab), and loads that tile's records only
-//   D(n - 1): that tile's depthwise in four k-slabs' time, 64 columns of t2
-//   P(n - 1): K = 64, two k-slabs
-// It reads the SAME packed weights (cop_pad a multiple of 128, nslab3 = cop_pad / 32): fragment indices of real channels are what they
-// were, and no fragment of the padded half is ever requested.  The padded channels contribute exact zeros to every sum and the real
-// channels are added in the order they were: the results are bit-equal to tower_x3_roles_kernel's, which CRA_X3_NO_TAIL selects
-// (tests/test_x3_tail_gpu.py compares the two).
+// tower_x3_quad_kernel is tower_x3_tail_kernel -- the same roles, barriers in the same order, packed weights, LDS regions, tail chunk
+// variants, gate phases and early request of the first window; the residual stream in the PROJECT waves' registers -- except:
+//   E: the expand MFMA takes the x fragment as A and the weight fragment as B (both have the same lane shape: the packing is what it
+//      was).  A lane then holds channel l15 of the tile on rows 4 lg + r of square tile t: with the row order of x3_row that is rank
+//      4 (lg >> 1) + t, file 4 (lg & 1) + r, a 4 x 4 quadrant of the board.  The row order, and with it staging, the epilogue's xh / xl
+//      stores, the store to HBM, the PROJECT accumulators' square order and the SE phases, are what they were.
+//   D: X3DepthwiseQuad (x3_quad.h): the taps are v_fmac_f32 on the lane's own registers, a halo of 4 + 4 + 1 values comes from lane
+//      groups lg ^ 1, lg ^ 2, lg ^ 3 through the LDS crossbar.  X3Depthwise::gather spends 16 half-rate DPP moves per channel.
+//   t2: stored as t2T[channel][square row] (x3q_t2t_offset: 128-byte rows, XOR swizzle, no padding) with one ds_write_b64 per rank and
+//      hi / lo, the count of before; the PROJECT waves read their B fragments with two ds_read_b64_tr_b16 each.  A fragment holds the k
+//      it held: the project sums add the same terms in the same positions.
+// Per output the depthwise arithmetic is tower_x3_tail_kernel's; the expand sums are the same products in the same order, but the
+// accumulation inside an MFMA is not specified to be the same with A and B swapped, so the two kernels are compared within a bound
+// (tests/test_x3_quad_gpu.py), not bit for bit.  3x3 runs only: launch_tower_x3 sends 5x5 runs to tower_x3_tail_kernel, and
+// CRA_X3_NO_QUAD every run.
 //
-// x3_quad.cpp (tower_x3_quad_kernel, the default of 3x3 runs) is a copy of this kernel that differs in three places, and a fix to the
-// schedule here -- role loops, load_e / load_p, the window logic, the tail variants, the stamps -- belongs there as well:
-//   1. the EXPAND wave's lane constants in front of its chunk loop and the operand order of the three expand x3_mfma calls;
-//   2. the depthwise pieces set between the k-slabs (load / gather / taps) and the half4 stores of their output to t2;
-//   3. the PROJECT wave's operand reads from t2.
+// Maintaining the two files: everything but three places is x3_tail.cpp's text -- the role loops, load_e / load_p and the window logic,
+// the tail chunk variants, the gate phases, the epilogue and the CRA_X3_TRACE stamps -- and a fix to that schedule belongs in BOTH.  The
+// three places that differ (x3_tail.cpp names the same three):
+//   1. the EXPAND wave's lane constants in front of its chunk loop (x3_quad_offsets and the t2T store offsets, where the tail kernel has
+//      x3_edge_offsets) and the operand order of the three expand x3_mfma calls;
+//   2. the depthwise pieces set between the k-slabs (X3DepthwiseQuad's load / gather / taps_rank, KS == 3 only, where the tail kernel
+//      has X3Depthwise's and X3Depthwise5's) and the half4 stores of their output (t2T offsets, where the tail kernel has [row][TROW]);
+//   3. the PROJECT wave's operand reads (x3q_read_fragment on offsets computed once in front of the chunk loop, where the tail kernel
+//      reads a half8 per square row).
 //
-// Why this kernel is in a .cpp file: tests/test_experts_isa.py pins the instruction text of every kernel in the library's .hip listings to
-// the commit before the expert sets and allows exactly four new function symbols there; it counts new symbols in .hip listings only and,
-// as an existing test, is not edited.  A kernel added to any .hip file fails it however good the kernel is.  build.sources() compiles
-// .cpp files as HIP as well, so the new kernel lives here, and the pin test keeps its meaning: no kernel that existed before moved
-// (the helpers both files share are in x3_device.h, and x3.hip's listing is what it was).
+// (Why a .cpp file: x3_tail.cpp.)
 #include "x3_device.h"
+#include "x3_quad.h"
 
 #include <type_traits>
 
 namespace cra {
 
 template <int KS>
-__global__ __launch_bounds__(512) void tower_x3_tail_kernel(const X3TowerArgs a) {
-    static_assert(KS == 3 || KS == 5, "depthwise 3x3 or 5x5 (X3Depthwise / X3Depthwise5)");
-    constexpr int REC = KS == 3 ? 256 : 512;                            // floats of depthwise records per 16-channel tile
+__global__ __launch_bounds__(512) void tower_x3_quad_kernel(const X3TowerArgs a) {
+    static_assert(KS == 3, "depthwise 3x3 (X3DepthwiseQuad); 5x5 runs stay on tower_x3_tail_kernel");
+    constexpr int REC = 256;                            // floats of depthwise records per 16-channel tile
     using G = X3Block;
     static_assert(G::NE == 1 && G::T2BUF == 2 && G::CK == 128, "the role kernel uses the NE = 1 tile geometry (two t2 buffers of 128 channels)");
+    static_assert(X3Q_T2T_HALVES <= 64 * G::TROW, "t2T of a chunk lies in the [64][TROW] tile's place");
     constexpr int C = G::C, CK = G::CK, XROW = G::XROW, TROW = G::TROW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const X3Tiles T = x3_tiles(smem);
@@ -78,8 +84,10 @@ __global__ __launch_bounds__(512) void tower_x3_tail_kernel(const X3TowerArgs a)
 #endif
         // barriers of a block, the same for both roles: one behind each of the halves 0 ... 2n, then the one behind the epilogue
         {
-            const bool hi = l15 >= 8;                                  // the tile's second rank (t + 4, x3_row)
-            const X3EdgeOffsets edge = x3_edge_offsets(l15);             // a lane on file a / h has no left / right neighbour on the board
+            const X3QuadOffsets qo = x3_quad_offsets(lane);              // which sides of the lane's quadrant are board edges (zero rows of the records)
+            int sto[4];                                                 // t2T offsets of the lane's four ranks (tile 0)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) sto[t] = x3q_store_offset(0, l15, lg, t);
             // expand weight window: EW of the 8 k-slabs x 2 channel tiles x (hi, lo); the stream runs on across chunk boundaries: slab s of
             // chunk i sits in slot s % EW and is refilled with the slab EW positions ahead right behind its MFMAs
             // cout tile (16 channels) of (chunk i, wave w, ne): i * 8 + w * 2 + ne; in the tail chunk the wave owns ONE tile, i * 8 + w (asked
@@ -114,9 +122,7 @@ __global__ __launch_bounds__(512) void tower_x3_tail_kernel(const X3TowerArgs a)
             if (!first_chunk_requested) load_first_chunk(W, tail && n == 1);
             float* const my_dws = T.dws + (w * 2) * REC;               // this wave's two record tiles
             f32x4 accE[2][4], accD[2][4];                               // chunk i being expanded / chunk i - 1 in the depthwise
-            X3Depthwise dw;
-            X3Depthwise5 dw5;
-            const X3EdgeOffsets5 edge5 = x3_edge_offsets5(l15);
+            X3DepthwiseQuad dw;
             // Interval i: E(i) (HASE) with D(i - 1) (HASD) cut into sixteen pieces, two per k-slab: tile 0 in slabs 0-3, tile 1 in 4-7.
             // ONEE: chunk i is the tail, E(i) expands the wave's one tile (half the MFMAs per k-slab); ONED: chunk i - 1 is the tail, D(i - 1) is
             // tile 0's eight pieces in four k-slabs' time and writes columns w * 16 ... of t2.  The tail is a block's last chunk: never both.
@@ -125,7 +131,7 @@ __global__ __launch_bounds__(512) void tower_x3_tail_kernel(const X3TowerArgs a)
                 constexpr bool ONEE = decltype(onee_c)::value, ONED = decltype(oned_c)::value;
                 static_assert(!(ONEE && !HASE) && !(ONED && (HASE || !HASD)), "the tail chunk is expanded in interval n - 1 and runs the depthwise alone in interval n");
                 constexpr int NEE = ONEE ? 1 : 2;                        // channel tiles E(i) expands
-                // stream fragments (B operands) through a ring of four (k-slab, square tile) steps: a step's pair (hi, lo) is requested
+                // stream fragments (A operands) through a ring of four (k-slab, square tile) steps: a step's pair (hi, lo) is requested
                 // three steps = 18 MFMAs ahead (a slab's eight pairs double-buffered would be 64 registers beside the depthwise's state)
                 half8 ring_h[4], ring_l[4];
                 auto read_step = [&](int st) {                          // step st = k-slab st / 4, square tile st % 4
@@ -152,22 +158,14 @@ __global__ __launch_bounds__(512) void tower_x3_tail_kernel(const X3TowerArgs a)
                         for (int t = 0; t < 4; ++t) accE[ne][t] = f32x4{0.f, 0.f, 0.f, 0.f};
                     read_step(0); read_step(1); read_step(2);
                 }
-                if constexpr (HASD && KS == 3) dw.template load<0>(my_dws, lg, edge);
+                if constexpr (HASD) dw.load(my_dws, l15, qo);
                 half_t* const t2h = T.t2h + ((i - 1) & 1) * 64 * TROW;
                 half_t* const t2l = T.t2l + ((i - 1) & 1) * 64 * TROW;
 #pragma unroll
                 for (int sl = 0; sl < (ONED ? C / 64 : C / 32); ++sl) {
                     const int dt = sl / 4, ph = sl % 4;                 // the depthwise's tile and quarter
                     if constexpr (HASD) {
-                        if constexpr (KS == 3) {
-                            if (ph == 2) dw.template load<1>(my_dws + dt * 256, lg, edge);
-                            if (sl == 4) dw.template load<0>(my_dws + 256, lg, edge);  // (tile 0's last pieces ran in slab 3)
-                        } else {                                        // 5x5: one channel of the tile per k-slab
-                            if (ph == 0) dw5.template load<0>(my_dws + dt * REC, lg, edge5);
-                            if (ph == 1) dw5.template load<1>(my_dws + dt * REC, lg, edge5);
-                            if (ph == 2) dw5.template load<2>(my_dws + dt * REC, lg, edge5);
-                            if (ph == 3) dw5.template load<3>(my_dws + dt * REC, lg, edge5);
-                        }
+                        if (!ONED && sl == 3) dw.load(my_dws + 256, l15, qo);   // tile 1's records (tile 0's last taps ran in slab 2)
                     }
                     __builtin_amdgcn_sched_barrier(0);
                     if constexpr (HASE) {
@@ -177,9 +175,9 @@ __global__ __launch_bounds__(512) void tower_x3_tail_kernel(const X3TowerArgs a)
                             if (st + 3 < 4 * (C / 32)) read_step(st + 3);
 #pragma unroll
                             for (int ne = 0; ne < NEE; ++ne) {
-                                x3_mfma(e_l[sl % EW][ne], ring_h[st % 4], accE[ne][t], !(X3_ABL & 2));
-                                x3_mfma(e_h[sl % EW][ne], ring_l[st % 4], accE[ne][t], !(X3_ABL & 2));
-                                x3_mfma(e_h[sl % EW][ne], ring_h[st % 4], accE[ne][t], !(X3_ABL & 2));
+                                x3_mfma(ring_h[st % 4], e_l[sl % EW][ne], accE[ne][t], !(X3_ABL & 2));      // x is A: D[row 4 lg + r][channel l15]
+                                x3_mfma(ring_l[st % 4], e_h[sl % EW][ne], accE[ne][t], !(X3_ABL & 2));
+                                x3_mfma(ring_h[st % 4], e_h[sl % EW][ne], accE[ne][t], !(X3_ABL & 2));
                             }
                         }
                         if (sl + EW < C / 32) load_e(onee_c, i, sl + EW);
@@ -187,28 +185,21 @@ __global__ __launch_bounds__(512) void tower_x3_tail_kernel(const X3TowerArgs a)
                         else load_e(onee_c, i + 1 < n ? i + 1 : i, sl + EW - C / 32);      // (the next chunk's tiles, e_tile: one tile twice if it is the tail)
                     }
                     if constexpr (HASD) {
-                        if constexpr (KS == 3) {
-                            if (ph == 0) dw.template gather<0>(accD[dt], hi);
-                            if (ph == 1) { dw.template taps<0>(0, 4); dw.pin_taps(0, 4, 0); }
-                            if (ph == 2) dw.template gather<1>(accD[dt], hi);
-                        } else {
-                            if (ph == 0) { dw5.template gather<0>(accD[dt], hi, 1.f); dw5.template taps<0>(); }
-                            if (ph == 1) { dw5.template gather<1>(accD[dt], hi, 1.f); dw5.template taps<1>(); }
-                            if (ph == 2) { dw5.template gather<2>(accD[dt], hi, 1.f); dw5.template taps<2>(); }
-                            if (ph == 3) { dw5.template gather<3>(accD[dt], hi, 1.f); dw5.template taps<3>(); }
-                        }
+                        // a tile's depthwise in four k-slabs: BN1 + ReLU and the halo exchange; ranks 0, 1; ranks 2, 3; split and store
+                        if (ph == 0) dw.gather(accD[dt], lg, qo);
+                        if (ph == 1) { dw.template taps_rank<0>(); dw.template taps_rank<1>(); dw.template pin_rank<0>(); dw.template pin_rank<1>(); }
+                        if (ph == 2) { dw.template taps_rank<2>(); dw.template taps_rank<3>(); dw.template pin_rank<2>(); dw.template pin_rank<3>(); }
                         if (ph == 3) {
-                            if constexpr (KS == 3) dw.template taps<1>(0, 4);
-                            const int cl = (ONED ? w : w * 2 + dt) * 16 + lg * 4;  // split -> t2 of chunk i - 1
+                            const int tile = ONED ? w : w * 2 + dt;            // split -> t2T of chunk i - 1: the lane's channel, its four files of rank t
 #pragma unroll
                             for (int t = 0; t < 4; ++t) {
                                 half4 h, l;
-                                split4(KS == 3 ? dw.outv[t] : dw5.outv[t], h, l);
+                                split4(dw.outv[t], h, l);
                                 if constexpr (X3_ABL & 64) {
                                     asm volatile("" ::"v"(h), "v"(l));
                                 } else {
-                                    *reinterpret_cast<half4*>(t2h + (t * 16 + l15) * TROW + cl) = h;
-                                    *reinterpret_cast<half4*>(t2l + (t * 16 + l15) * TROW + cl) = l;
+                                    *reinterpret_cast<half4*>(t2h + tile * 16 * X3Q_T2T_ROW + sto[t]) = h;
+                                    *reinterpret_cast<half4*>(t2l + tile * 16 * X3Q_T2T_ROW + sto[t]) = l;
                                 }
                             }
                         }
@@ -283,6 +274,11 @@ __global__ __launch_bounds__(512) void tower_x3_tail_kernel(const X3TowerArgs a)
             // project weight window: 2 of a chunk's 4 k-slabs x 4 cout tiles x (hi, lo), running on across chunk boundaries
             constexpr int PW = 2;
             half8 p_h[PW][NJ], p_l[PW][NJ];
+            int rdo[2][4];                                              // t2T offsets of the lane's transposed reads (every lane supplies one, in bounds: EXEC is all ones here)
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) rdo[hh][t] = x3q_read_offset(0, hh, t, l15, lg);
             auto load_p = [&](int k, int s2) {                         // cout tile = w * 4 + j, K slab = k * 4 + s2
                 if constexpr (X3_ABL & 16) return;
 #pragma unroll
@@ -312,6 +308,12 @@ __global__ __launch_bounds__(512) void tower_x3_tail_kernel(const X3TowerArgs a)
                 constexpr int NS2 = decltype(one_c)::value ? CK / 64 : CK / 32;
                 const half_t* const t2h = T.t2h + (kk & 1) * 64 * TROW;
                 const half_t* const t2l = T.t2l + (kk & 1) * 64 * TROW;
+                const half_t* rd[2][4];                                  // the lane's addresses in k-slab 0 (x3q_read_offset)
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) rd[hh][t] = t2h + rdo[hh][t];
+                const int to_lo = int(t2l - t2h);
                 X3_STAMP(8);
                 half8 bh[2][4], bl[2][4];
                 auto read_t2 = [&](int s2, half8 (&h)[4], half8 (&l)[4]) {
@@ -321,8 +323,8 @@ __global__ __launch_bounds__(512) void tower_x3_tail_kernel(const X3TowerArgs a)
                             h[t] = p_h[s2 % PW][0];
                             l[t] = p_l[s2 % PW][0];
                         } else {
-                            h[t] = *reinterpret_cast<const half8*>(t2h + (t * 16 + l15) * TROW + s2 * 32 + lg * 8);
-                            l[t] = *reinterpret_cast<const half8*>(t2l + (t * 16 + l15) * TROW + s2 * 32 + lg * 8);
+                            h[t] = x3q_read_fragment(rd[0][t] + s2 * 32 * X3Q_T2T_ROW, rd[1][t] + s2 * 32 * X3Q_T2T_ROW);
+                            l[t] = x3q_read_fragment(rd[0][t] + s2 * 32 * X3Q_T2T_ROW + to_lo, rd[1][t] + s2 * 32 * X3Q_T2T_ROW + to_lo);
                         }
                     }
                 };
@@ -377,13 +379,11 @@ __global__ __launch_bounds__(512) void tower_x3_tail_kernel(const X3TowerArgs a)
     }
 }
 
-void init_x3_tail_kernel_attributes() {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tower_x3_tail_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, int(X3Block::lds_bytes));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tower_x3_tail_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, int(X3Block::lds_bytes + 8192));
+void init_x3_quad_kernel_attributes() {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tower_x3_quad_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, int(X3Block::lds_bytes));
 }
-void launch_tower_x3_tail(const X3TowerArgs& a, hipStream_t s) {
-    if (a.ks == 5) hipLaunchKernelGGL(tower_x3_tail_kernel<5>, dim3(a.batch), dim3(X3Block::NTHR), X3Block::lds_bytes + 8192, s, a);    // (2 KiB of records per tile)
-    else hipLaunchKernelGGL(tower_x3_tail_kernel<3>, dim3(a.batch), dim3(X3Block::NTHR), X3Block::lds_bytes, s, a);
+void launch_tower_x3_quad(const X3TowerArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(tower_x3_quad_kernel<3>, dim3(a.batch), dim3(X3Block::NTHR), X3Block::lds_bytes, s, a);
 }
 
 }  // namespace cra

@@ -184,6 +184,16 @@ class HipAPI:
             raise RuntimeError(_capi.last_error())
         return [(names[i].decode(), ms[i] / iters) for i in range(n)]
 
+    def op_kernels(self):
+        """mi_net_op_kernel of every op: the kernel each launch of a forward goes to (time_ops' names where an op has one kernel)."""
+        out = []
+        for i in range(self._lib.mi_net_op_count(self._h)):
+            name = self._lib.mi_net_op_kernel(self._h, i)
+            if name is None:
+                raise RuntimeError(_capi.last_error())
+            out.append(name.decode())
+        return out
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._lib.mi_net_destroy(self._h)

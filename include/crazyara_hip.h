@@ -136,6 +136,9 @@ int mi_net_time_forward(mi_net* net, int iters, float* ms_total);
  * names: op_count pointers to static strings; ms: op_count accumulated milliseconds (sum over iters). */
 int mi_net_op_count(const mi_net* net);
 int mi_net_time_ops(mi_net* net, int iters, const char** names, float* ms);
+/* The kernel op `op` launches, where one op name covers several kernels ("tower_x3": "tower_x3_quad_kernel<3>", "tower_x3_tail_kernel<3>",
+ * ... as the launch itself chooses); the op's name otherwise.  A static string; NULL + mi_last_error when there is no such op. */
+const char* mi_net_op_kernel(const mi_net* net, int op);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Environment: position, legal moves, terminal rules (State interface of engine/src/state.h:287-509 as implemented by

@@ -12,6 +12,9 @@ O8 = [list(range(i, i + 8)) for i in range(0, 64, 8)]
 KINDS = {   # groups, bank modulus (dwords), dwords per lane
     "ds_read_b128": (G128, 64, 4), "ds_read_b64": (HALVES, 64, 2), "ds_read_b32": (HALVES, 32, 1),
     "ds_write_b32": (HALVES, 32, 1), "ds_write_b64": (Q16, 32, 2), "ds_write_b128": (O8, 32, 4),
+    # the transposed read of tower_x3_quad_kernel: every lane supplies an 8-byte address as for ds_read_b64, the exchange between the lanes
+    # of a 16-lane group comes after the banks: groups are the 32-lane halves, bank (a / 4) % 64
+    "ds_read_b64_tr_b16": (HALVES, 64, 2),
 }
 
 
@@ -115,3 +118,38 @@ def search():
 
 if __name__ == "__main__":
     search()
+
+
+def quad_layouts():
+    """t2T[channel][square row] of tower_x3_quad_kernel (x3_quad.h): candidate row pitches and unit swizzles for the EXPAND lanes' half4
+    stores (ds_write_b64, 16 channels of a tile at one 4-row unit) and the PROJECT lanes' transposed reads (ds_read_b64_tr_b16: lane
+    (l15, lg) names channel s2 * 32 + lg * 8 + hh * 4 + (l15 >> 2), unit 4 t + (l15 & 3)).  The offsets are x3q_store_offset /
+    x3q_read_offset re-stated; tests/test_x3_quad_maps.py checks the header's own functions with the same bank rule."""
+    lg = lambda l: l >> 4
+    l15 = lambda l: l & 15
+    bits = lambda c, order: sum(((c >> b) & 1) << i for i, b in enumerate(order))
+    swizzles = {
+        "none": lambda c: 0,
+        "c & 15": lambda c: c & 15,
+        "bits (0, 2, 1, 3) of c [shipped: x3q_swizzle]": lambda c: bits(c, (0, 2, 1, 3)),
+        "bits (1, 0, 3, 2) of c": lambda c: bits(c, (1, 0, 3, 2)),
+    }
+    print("t2T rows: pitch (bytes), unit swizzle -> E half4 stores (32 per chunk and wave) + P transposed reads (32 per chunk and tile), "
+          "cycles; conflict-free: 128 + 64")
+    out = []
+    for pitch in (128, 136, 144):
+        for name, sw in swizzles.items():
+            if pitch != 128 and name != "none":
+                continue                                   # (a swizzle over 16 units needs the 128-byte row; padding is the alternative)
+            off = lambda c, unit: c * pitch + 8 * (unit ^ sw(c & 15))
+            wr = sum(cycles("ds_write_b64", lambda l, tile=tile, t=t: off(tile * 16 + l15(l), 4 * t + lg(l)))[0]
+                     for tile in range(8) for t in range(4))
+            rd = sum(cycles("ds_read_b64_tr_b16", lambda l, s2=s2, hh=hh, t=t: off(s2 * 32 + lg(l) * 8 + hh * 4 + (l15(l) >> 2), 4 * t + (l15(l) & 3)))[0]
+                     for s2 in range(4) for hh in range(2) for t in range(4))
+            out.append((wr + rd, pitch, name, wr, rd))
+    for tot, pitch, name, wr, rd in sorted(out):
+        print(f"  pitch {pitch}, swizzle {name}: stores {wr} + reads {rd} = {tot}   (LDS bytes per buffer {128 * pitch})")
+
+
+if __name__ == "__main__":
+    quad_layouts()

@@ -11,7 +11,8 @@
 #include <vector>
 
 #include "x3.hip"        // -I crazyara_amd/csrc/nn
-#include "x3_tail.cpp"   // tower_x3_tail_kernel, the default two-role tower (CRA_X3_NO_TAIL=1: tower_x3_roles_kernel)
+#include "x3_tail.cpp"   // tower_x3_tail_kernel (CRA_X3_NO_QUAD=1), its 64-channel tail chunk (CRA_X3_NO_TAIL=1: tower_x3_roles_kernel)
+#include "x3_quad.cpp"   // tower_x3_quad_kernel, the default two-role tower of 3x3 runs: transposed expand accumulators
 namespace cra { size_t value_head_lds_bytes(const ValueHeadArgs&) { return 0; } }      // (kernels.hip's, which this harness does not link: the head launches are not used here)
 
 #define CK(e) do { hipError_t _e = (e); if (_e != hipSuccess) { fprintf(stderr, "HIP error %s at %s\n", hipGetErrorString(_e), #e); exit(1); } } while (0)
@@ -66,6 +67,7 @@ int main(int argc, char** argv) {
         const char* tw = getenv("CRA_X3_TOWER");
         a.symmetric = tw && std::string(tw) == "symmetric" ? 1 : 0;
         a.no_tail = getenv("CRA_X3_NO_TAIL") != nullptr;         // (RiseNet::DevSwitches::x3_no_tail)
+        a.no_quad = getenv("CRA_X3_NO_QUAD") != nullptr;         // (RiseNet::DevSwitches::x3_no_quad)
     }
     init_x3_kernel_attributes();
     hipStream_t s;
