@@ -435,6 +435,8 @@ struct HeadsSmallArgs {
 };
 bool heads_small_fits(const ConvArgs& c, const ValueHeadArgs& v);
 void launch_heads_small(const HeadsSmallArgs& a, hipStream_t s);
+// (nets made for MORE than 64 boards, float16x3: the policy chain with the value head on the two waves its second conv leaves idle --
+// conv3x3_x3_heads_kernel, x3_heads.h / x3_heads.cpp)
 
 // last stage of the value head, one wave per board.
 //  tanh head : value = tanh(b2 + dot(w2, h[b]))            h: [B][fc] T (FC1 + ReLU output of the conv_gemm "FC" launch)

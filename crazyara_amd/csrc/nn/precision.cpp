@@ -34,6 +34,8 @@ RiseNet::DevSwitches::DevSwitches() {
     x3_no_tail = getenv("CRA_X3_NO_TAIL") != nullptr;
     x3_no_quad = getenv("CRA_X3_NO_QUAD") != nullptr;
     small_batch_heads_apart = getenv("CRA_SMALL_BATCH_HEADS_APART") != nullptr;
+    if (const char* e = getenv("CRA_X3_HEADS_APART")) x3_heads_apart = e[0] != '0' && e[0] != 0;
+    value_head_env = getenv("CRA_X3_VALUE_HEAD") != nullptr || getenv("CRA_VALUE_HEAD_VARIANT") != nullptr;
 }
 
 Precision parse_precision(const std::string& precision) {

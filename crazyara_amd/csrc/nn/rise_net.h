@@ -124,7 +124,7 @@ public:
     // per-launch bookkeeping (bench.py roofline: live hipEvent timing of each op on the net stream)
     int launches_per_forward() const { return launches_; }
     const char* op_name(int i) const;
-    const char* op_kernel(int i) const;                // the kernel op i launches where one op name covers several (tower_x3: launch_tower_x3's choice), else op_name(i)
+    const char* op_kernel(int i) const;                // the kernel op i launches where one op name covers several (tower_x3: launch_tower_x3's choice; float16x3's policy chain: conv3x3_x3_chain_kernel or, with the value head on its idle waves, conv3x3_x3_heads_kernel), else op_name(i)
     void time_ops(int iters, float* ms);               // ms[i] += elapsed of op i, summed over iters (un-graphed launches)
     float time_forward(int iters);                     // graph replays between two events, returns ms
 
@@ -190,6 +190,8 @@ private:
         bool x3_no_tail = false;        // CRA_X3_NO_TAIL: the float16x3 two-role tower runs every chunk at 128 channels (tower_x3_roles_kernel)
         bool x3_no_quad = false;        // CRA_X3_NO_QUAD: the float16x3 two-role tower's 3x3 runs stay on tower_x3_tail_kernel (not tower_x3_quad_kernel)
         bool small_batch_heads_apart = false;   // CRA_SMALL_BATCH_HEADS_APART: a small batch's policy conv and value head as two launches
+        bool x3_heads_apart = false;    // CRA_X3_HEADS_APART: the float16x3 policy chain and the value head as two launches also above 64 boards (A/B reference of conv3x3_x3_heads_kernel)
+        bool value_head_env = false;    // CRA_X3_VALUE_HEAD or CRA_VALUE_HEAD_VARIANT is set, whatever to: the value head is asked for by kernel, it keeps its own launch
         DevSwitches();
     } dev_;
     float* value_head_dbg_ = nullptr;

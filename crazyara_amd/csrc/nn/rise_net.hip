@@ -105,7 +105,17 @@ template <typename T> void RiseNet::launch_op(int i, hipStream_t s, ForwardCall&
             launch_planes_to_act<T>(op.x == d_planes_ ? planes : static_cast<const float*>(op.x), static_cast<T*>(op.y), B, op.C, im.cin_pad, s);
             break;
         case OpKind::Conv:
-            if (prec_.x3() && dev_.conv_dev >= 0) {                                // development: bisecting switches of conv_gemm_x3_kernel
+            if (op.heads_x3) {                               // the policy chain with the value head on its idle waves (x3_heads.cpp)
+                HeadsX3Args h;
+                h.conv = boards(op.conv);
+                h.conv.softmax_out = probs;
+                if (!keep_logits_) h.conv.out = nullptr;
+                h.vh = op.vh;
+                h.vh.value = value;
+                h.vh.aux = aux;
+                h.vh.batch = h.conv.batch;
+                launch_heads_x3(h, s);
+            } else if (prec_.x3() && dev_.conv_dev >= 0) {                                // development: bisecting switches of conv_gemm_x3_kernel
                 ConvArgs c = boards(op.conv);
                 c.dev = dev_.conv_dev;
                 if (op.from_planes) c.planes = planes;
@@ -290,6 +300,8 @@ const char* RiseNet::op_name(int i) const {
 
 const char* RiseNet::op_kernel(int i) const {
     const Op& op = impl_->ops.at(i);
+    if (op.kind == OpKind::Conv && op.heads_x3) return kHeadsX3KernelName;
+    if (op.kind == OpKind::Conv && prec_.x3() && !op.conv.p8 && op.conv.pre_wpk) return "conv3x3_x3_chain_kernel";      // (launch_conv_gemm_x3's first branch)
     return op.kind == OpKind::TowerX3 ? tower_x3_kernel_name(op.tx) : op_name(i);
 }
 

@@ -102,6 +102,7 @@ template <typename T> struct RiseNet::Builder {
     void policy_head();
     void softmax();
     void value_head();
+    void merge_heads_x3();
     void merge_heads_small();
     void merge_forward();
 };
@@ -1053,6 +1054,23 @@ template <typename T> void RiseNet::Builder<T>::merge_heads_small() {
     }
 }
 
+// Precision float16x3, a net made for more than 64 boards: the policy chain's second conv has at most six cout tiles for eight waves, and
+// the value head runs on the two idle ones (x3_heads.cpp: conv3x3_x3_heads_kernel, the bits of the two launches).  The op stays a Conv op
+// with the chain's name; it carries the value head's arguments too.  Nets for at most 64 boards keep their heads (heads_small / value_head:
+// the small-batch path and the co-residency screen work on those); CRA_X3_VALUE_HEAD / CRA_VALUE_HEAD_VARIANT ask for a value head kernel
+// by name and get its launch; CRA_X3_HEADS_APART=1: the A/B reference.
+template <typename T> void RiseNet::Builder<T>::merge_heads_x3() {
+    std::vector<Op>& ops = im.ops;
+    if (!(prec.x3() && !prec.p8() && B > RiseNet::kBoardSplitMaxBatch && !dev.x3_heads_apart && !dev.value_head_env && dev.conv_dev < 0)) return;
+    if (ops.size() < 2 || ops.back().kind != OpKind::ValueHead || ops[ops.size() - 2].kind != OpKind::Conv) return;
+    const Op& pol = ops[ops.size() - 2];
+    if (!pol.fused_softmax || pol.from_planes || !heads_x3_fits(pol.conv, ops.back().vh) || pol.conv.batch != ops.back().vh.batch) return;
+    const ValueHeadArgs vh = ops.back().vh;
+    ops.pop_back();
+    ops.back().heads_x3 = true;
+    ops.back().vh = vh;
+}
+
 // stem -> tower -> head with nothing in between and nothing handed to other launches: one launch, the board tile stays in LDS
 template <typename T> void RiseNet::Builder<T>::merge_forward() {
     std::vector<Op>& ops = im.ops;
@@ -1090,9 +1108,11 @@ template <typename T> void RiseNet::build(const NetFile& nf) {
         b.softmax();
         b.value_head();
         b.merge_heads_small();
+        b.merge_heads_x3();
     }
     init_block_kernel_attributes<T>();
     init_x3_kernel_attributes();
+    init_x3_heads_kernel_attributes();
     init_x3_wblock_kernel_attributes();
     init_x3_wsplit_kernel_attributes();
     init_x3_wtower_kernel_attributes();

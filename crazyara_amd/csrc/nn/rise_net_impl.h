@@ -8,6 +8,7 @@
 
 #include "kernels.h"
 #include "rise_net.h"
+#include "x3_heads.h"
 
 namespace cra {
 
@@ -25,6 +26,7 @@ struct Op {
     ConvArgs conv{};
     bool from_planes = false;     // float16x3 stem conv: reads the NCHW input planes (their address is a launch-time value too)
     bool fused_softmax = false;   // float16x3 policy-map conv: the softmax runs in its launch (the probabilities' address is a launch-time value)
+    bool heads_x3 = false;        // float16x3 policy chain that also runs the value head `vh` (x3_heads.cpp: conv3x3_x3_heads_kernel; Builder::merge_heads_x3)
     // depthwise / se
     const void* x = nullptr;
     void* y = nullptr;

@@ -41,7 +41,7 @@ ap.add_argument("--cross", default="", help="victim:aggressor config pairs, comm
 ap.add_argument("--search", action="store_true", help="add a live two-lane search of the aggressor's model as one more aggressor")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
-os.environ["CRA_X3_VALUE_HEAD"] = "one"
+os.environ["CRA_X3_VALUE_HEAD"] = "one"      # (also keeps the op named value_head above 64 boards: a net told its value head kernel does not run it inside conv3x3_x3_heads_kernel)
 if args.fence:
     os.environ["CRA_VALUE_HEAD_LDS_PAD"] = "0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

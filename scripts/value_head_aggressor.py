@@ -11,7 +11,7 @@ import sys
 import tempfile
 import threading
 
-os.environ["CRA_X3_VALUE_HEAD"] = "one"
+os.environ["CRA_X3_VALUE_HEAD"] = "one"      # (also keeps the op named value_head above 64 boards: a net told its value head kernel does not run it inside conv3x3_x3_heads_kernel)
 os.environ["CRA_VALUE_HEAD_DEBUG"] = "1"
 os.environ.setdefault("CRA_VALUE_HEAD_LDS_PAD", "-1")      # the round-3 form that shares compute units (0 = the shipped, exclusive form)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -22,7 +22,7 @@ import tempfile
 import threading
 from collections import Counter
 
-os.environ["CRA_X3_VALUE_HEAD"] = "one"
+os.environ["CRA_X3_VALUE_HEAD"] = "one"      # (also keeps the op named value_head above 64 boards: a net told its value head kernel does not run it inside conv3x3_x3_heads_kernel)
 os.environ["CRA_VALUE_HEAD_DEBUG"] = "1"
 os.environ.setdefault("CRA_VALUE_HEAD_LDS_PAD", "-1")
 os.environ["CRA_VALUE_HEAD_VARIANT"] = str(16 | int(os.environ.get("ROOTCAUSE_EXTRA_VARIANT", "0")))
