@@ -357,7 +357,10 @@ TowerBlockPack pack_tower_block(const BlockFold& bf, int C, int cop, int k, int 
     // Precision int8 (oracle/rise_oracle.py: int8_block is the definition): s1 / s3 = max |row| / 127, weights rounded half to
     // even; with the block's calibrated activation steps 1 / qx_inv (stream) and 1 / qt_inv (depthwise output) a unit of the
     // expand accumulator is worth k1 = s1 / qx_inv, of the project accumulator k3 = s3 / qt_inv: the biases enter the
-    // accumulators as round(b / k), t1 = relu(acc) * 2^-7, k1 * 2^7 goes into the depthwise weights, y = x + k3 * acc
+    // accumulators as round(b / k), t1 = relu(acc) * 2^-7, k1 * 2^7 goes into the depthwise weights, y = x + k3 * acc.
+    // A row whose weights are zero (or nothing) beside its bias -- BatchNorm gamma = 0 with a bias, a constant channel -- would get a
+    // unit that the bias does not fit: the unit is then taken from the bias (2^14 units in the expand accumulator: t1 = 128, an f16
+    // integer; 2^24 in the project accumulator) and the row's weight bytes round to what is left of them in that unit.
     std::vector<double> s1(size_t(cop_pad), 1.0), s3(size_t(C), 1.0);
     std::vector<double> k1(size_t(cop_pad), 1.0), k3(size_t(C), 1.0);
     constexpr double kInt8Escale = 1.0 / 128.0;
@@ -380,12 +383,20 @@ TowerBlockPack pack_tower_block(const BlockFold& bf, int C, int cop, int k, int 
             for (int k2 = 0; k2 < C; ++k2) m = std::max(m, std::fabs(f1.w[size_t(ch) * C + k2]));
             s1[ch] = int8 ? std::max(m, 1e-30) / 127.0 : row_scale_pow2(m);
             k1[ch] = s1[ch] / qx_inv;
+            if (std::fabs(f1.b[ch]) > k1[ch] * 4194304.0) {                 // round(b / k1) * 2^-7 would leave the f16 range of t1
+                k1[ch] = std::fabs(f1.b[ch]) / 16384.0;
+                s1[ch] = k1[ch] * qx_inv;
+            }
         }
         for (int co = 0; co < C; ++co) {
             double m = 0;
             for (int ch = 0; ch < cop; ++ch) m = std::max(m, std::fabs(f3.w[size_t(co) * cop + ch]));
             s3[co] = int8 ? std::max(m, 1e-30) / 127.0 : row_scale_pow2(m);
             k3[co] = s3[co] / qt_inv;
+            if (std::fabs(f3.b[co]) > k3[co] * 1073741824.0) {              // round(b / k3) would leave the int32 accumulator
+                k3[co] = std::fabs(f3.b[co]) / 16777216.0;
+                s3[co] = k3[co] * qt_inv;
+            }
         }
         for (int w = 0; w < 4; ++w)
             for (int c = 0; c < n; ++c) {

@@ -3,6 +3,8 @@ ORACLE (test infrastructure only -- never imported by the product path).
 
 CPU fp32 restatement of the reference's RISE network forward pass, written as plain
 functional torch ops on a state-dict that uses the reference's own parameter names.
+forward() computes in the dtype of the state dict: on to_double(sd) it is the float64
+reference that the fp32 forward and the device modes are measured against.
 
 Follows (reference file:line, relative to /root/reference):
   * RiseV3.forward / layer order ........ DeepCrazyhouse/src/domain/neural_net/architectures/pytorch/rise_mobile_v3.py:81-184
@@ -44,6 +46,13 @@ from crazyara_amd.rise_config import (RiseConfig, rise_v2_config, rise_v33_confi
 # --------------------------------------------------------------------------------------------------------------
 # forward
 # --------------------------------------------------------------------------------------------------------------
+def to_double(sd):
+    """A float64 copy of a state dict (integer entries such as num_batches_tracked are kept).  forward() and _heads() compute in the dtype
+    of the state dict they are given, so forward(cfg, to_double(sd), x) is the high-precision reference of the fp32 forward; the
+    emulations of the device modes below stay fp32: they model device arithmetic."""
+    return {k: (v.double() if v.is_floating_point() else v.clone()) for k, v in sd.items()}
+
+
 def _bn(sd, name, x):
     return F.batch_norm(x, sd[name + ".running_mean"], sd[name + ".running_var"],
                         sd[name + ".weight"], sd[name + ".bias"], training=False, eps=BN_EPS)
@@ -56,10 +65,11 @@ def _q(x, sim_dtype):
 
 @torch.no_grad()
 def forward(cfg: RiseConfig, sd: Dict[str, torch.Tensor], x: torch.Tensor, sim_dtype=None, taps: dict = None):
-    """Returns (value[B,1], policy_logits[B,P*64], aux[B,4] or None).  x: [B,C,8,8] fp32."""
+    """Returns (value[B,1], policy_logits[B,P*64], aux[B,4] or None).  x: [B,C,8,8]; computed in the dtype of the state dict (fp32 as
+    make_state_dict gives it, float64 behind to_double; sim_dtype is for fp32 state dicts)."""
     W = (lambda n: sd[n]) if sim_dtype is None else (lambda n: sd[n].to(sim_dtype).to(torch.float32))
-    x = x.to(torch.float32)
     pre = cfg.key_prefix
+    x = x.to(sd[pre + ".0.body.0.weight"].dtype)
     h = F.relu(_bn(sd, pre + ".0.body.1", F.conv2d(_q(x, sim_dtype), W(pre + ".0.body.0.weight"), padding=1)))
     h = _q(h, sim_dtype)
     if taps is not None:
@@ -253,7 +263,8 @@ def predict_fp8_tower(cfg, sd, x):
 #   * activations: ONE step per tensor and block, fixed by calibration (max |.| over the calibration positions -> 127 for the stream in
 #     front of the block, -> 255 for the post-ReLU depthwise output, which is stored as u - 128); the quantiser is one f16 FMA
 #     x * inv + 1536 (1152) -- a single rounding to the integer grid, half to even -- clamped; inv is an f16 number and the step is 1 / inv;
-#   * weights: one step per output row (max |row| / 127), round half to even;
+#   * weights: one step per output row (max |row| / 127), round half to even; a row that is nothing beside its bias (a constant channel:
+#     BN gamma = 0, bias != 0) takes its accumulator unit from the bias instead (int8_block);
 #   * the BN1 / BN3 biases enter the integer accumulators rounded to the accumulator's unit;
 #   * t1 = f16(relu(acc) * 2^-7), depthwise in f16 with the dequantisation factors folded into its weights, stream and heads as float16.
 # calib = [(max|x_i|, max t2_i)] per block (calibrate_int8 below, or the library's mi_net_calibrate_int8 through the float16 layer kernels).
@@ -285,12 +296,18 @@ def int8_block(cfg: RiseConfig, sd, i: int, h: torch.Tensor, inv_x: float, inv_t
     w3, b3 = _fold(sd, p + ".body.6", p + ".body.7")
     s1 = w1.abs().amax(dim=(1, 2, 3)).clamp_min(1e-30) / 127.0
     s3 = w3.abs().amax(dim=(1, 2, 3)).clamp_min(1e-30) / 127.0
+    k1 = s1 / inv_x                                                              # value of one unit of the expand accumulator, per row
+    k3 = s3 / inv_t
+    # a row with (next to) nothing beside its bias -- a constant channel, BN gamma = 0 -- takes its unit from the bias: round(b1 / k1) *
+    # 2^-7 must stay an f16 number (t1), round(b3 / k3) an int32
+    big1, big3 = b1.abs() > k1 * 2.0 ** 22, b3.abs() > k3 * 2.0 ** 30
+    k1 = torch.where(big1, b1.abs() / 2.0 ** 14, k1)
+    k3 = torch.where(big3, b3.abs() / 2.0 ** 24, k3)
+    s1, s3 = torch.where(big1, k1 * inv_x, s1), torch.where(big3, k3 * inv_t, s3)
     q1 = torch.round(w1 / s1.view(-1, 1, 1, 1)).clamp(-127, 127)
     q3 = torch.round(w3 / s3.view(-1, 1, 1, 1)).clamp(-127, 127)
     if collect is not None:
         collect.append([float(h.abs().max()), 0.0])
-    k1 = s1 / inv_x                                                              # value of one unit of the expand accumulator, per row
-    k3 = s3 / inv_t
     qx = torch.round(h.double() * inv_x).clamp(-127, 127)                        # f16 x f16 is exact in double; one rounding, half to even
     acc = F.conv2d(qx, q1) + torch.round(b1 / k1).view(1, -1, 1, 1)
     t = _f16((F.relu(acc) * INT8_ESCALE).float())                                # t1

@@ -68,8 +68,9 @@ def _bottleneck(sd, p, se, k, h):
 
 @torch.no_grad()
 def forward(cfg, sd, x, uniform_attention=False):
-    """(value [B, 1], policy logits [B, P*64], aux [B, 4] or None) of a RiseV3 net whose blocks may be NTBs.  x: [B, C, 8, 8]."""
-    x = x.to(torch.float32)
+    """(value [B, 1], policy logits [B, P*64], aux [B, 4] or None) of a RiseV3 net whose blocks may be NTBs.  x: [B, C, 8, 8]; computed
+    in the dtype of the state dict (float64 behind oracle.rise_oracle.to_double)."""
+    x = x.to(sd["body_spatial.0.body.0.weight"].dtype)
     h = F.relu(ro._bn(sd, "body_spatial.0.body.1", F.conv2d(x, sd["body_spatial.0.body.0.weight"], padding=1)))
     for i, (k, se) in enumerate(zip(cfg.kernels, cfg.se_types)):
         p = f"body_spatial.{i + 1}"
